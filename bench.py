@@ -7,9 +7,19 @@ of NaiveObjectStateEstimator at 224x224, 256 images per GPU, bf16 compute / fp32
     python bench.py --gpus 1 --steps 20 --warmup 5
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0.  `roofline` is for the dominant kernel family of the step (HIP-event timed in
-a separate profiled pass after the timed region); `cpu_baseline` is the oracle (a CPU port of the reference
-path) timed on this box's host cores on a bounded sample (rank 0, N = 1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the line (images/s,
+ms_per_step).  With --full it also measures what the headline figure does not need, after the timed region:
+`host_issue_ms_per_step` (isolated steps), `roofline` for the dominant kernel of the step (HIP-event timed in a separate
+profiled pass) and, on rank 0 with N = 1, `cpu_baseline` (the oracle, a CPU port of the reference path, timed on the
+host's cores on a bounded sample), `pose_parity` and `f32_path`.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32, a few MB): the step's loss and
+val metrics, the model's pose outputs, and a fixed sample of the updated parameters, of their gradients and of the BN
+running statistics.  Inputs and initial weights are seeded, and the state is reset to them after the pre-conditioning
+windows, so two runs with the same arguments compute the same W + N steps.
 """
 import argparse
 import ctypes
@@ -125,6 +135,47 @@ def time_f32_path(dev, batch_size):
     return {"ms_per_step": round(dt * 1e3, 2), "images_per_s": round(batch_size / dt, 1), "steps": n}
 
 
+def snapshot_state(model, opt):
+    """Copies of everything a train step updates: parameters and BN buffers, Adam's moments and step count, the fp16 loss scale."""
+    scaler = getattr(model, "loss_scaler", None)
+    return ({k: v.detach().clone() for k, v in model.state_dict().items()},
+            {k: v.clone() if torch.is_tensor(v) else v for k, v in opt.state_dict().items()},
+            None if scaler is None else scaler.state_dict())
+
+
+def restore_state(model, opt, snap):
+    sd, osd, ssd = snap
+    model.load_state_dict(sd)
+    opt.load_state_dict(osd)
+    if ssd is not None:
+        model.loss_scaler.load_state_dict(ssd)
+
+
+DUMP_SAMPLE = 4096   # elements kept per parameter tensor in --dump-outputs (smaller tensors whole)
+
+
+def dump_outputs(path, model, step_out, model_out):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files.  `step_out` is train_step's
+    (loss, pos_err, ori_err), `model_out` the model's outputs of that step.  The parameters after the Adam update and their
+    gradients are sampled at the same seeded positions per tensor (named_parameters order); the BN running statistics are whole."""
+    import numpy as np
+    if not model_out:
+        raise RuntimeError("--dump-outputs: the model's outputs of the last timed step were not captured")
+    os.makedirs(path, exist_ok=True)
+    arrays = dict(zip(("loss", "pos_err", "ori_err"), step_out))
+    arrays.update(zip(("pose",) if len(model_out) == 1 else ("x0_pose", "x1_pose"), model_out))
+    params = [p for _, p in model.named_parameters()]
+    rng = np.random.default_rng(0)
+    pick = [None if p.numel() <= DUMP_SAMPLE else torch.from_numpy(np.sort(rng.integers(0, p.numel(), DUMP_SAMPLE))).to(p.device) for p in params]
+    take = lambda ts: torch.cat([t.detach().reshape(-1).float() if i is None else t.detach().reshape(-1).float()[i] for t, i in zip(ts, pick)])
+    arrays["param_sample"] = take(params)
+    arrays["grad_sample"] = take([torch.zeros_like(p) if p.grad is None else p.grad for p in params])
+    arrays["bn_buffers"] = torch.cat([b.detach().reshape(-1).float() for _, b in model.named_buffers() if b.is_floating_point()])
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().float().cpu().numpy())
+    log("[bench] wrote %d arrays to %s" % (len(arrays), path))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -132,7 +183,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=256, help="images per GPU")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f16", "f32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline, pose_parity and f32_path")
+    ap.add_argument("--full", action="store_true", help="after the timed region also measure host_issue_ms_per_step, the roofline profile pass and "
+                    "(N = 1, default model) cpu_baseline, pose_parity and f32_path")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy (float32)")
     ap.add_argument("--precondition-min", type=float, default=PRECONDITION_MIN_S,
                     help="least seconds of untimed 10-step windows before the W warm-up steps")
     ap.add_argument("--model", default="no", choices=["no", "n", "td", "tdo", "tdo_v2"],
@@ -145,6 +199,8 @@ def main():
                     "(parameter broadcast, staged stream joins, bucketed SUM all-reduce) so that its cost on one GPU is measured")
     ap.add_argument("--graph", action="store_true", help="replay one captured hipGraph per step instead of issuing every launch (N = 1 only; measured SLOWER than eager issue here: the host already runs ahead of the device and the replay schedules the two-stream backward worse -- DESIGN.md section 6)")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     from rgb_proprioceptive_pose_estimator_amd import models as M
     from rgb_proprioceptive_pose_estimator_amd._lib import RPE_F32, lib
@@ -187,6 +243,14 @@ def main():
     with contextlib.redirect_stdout(sys.stderr):  # the constructor prints its feature width, as the reference does; stdout is the JSON line only
         model = builders[args.model]()
     model.cuda().train()
+    # --dump-outputs: a forward hook keeps the model's outputs of the last timed step.  Eager: registered just before that step,
+    # so no other step runs the callback.  --graph: registered before the capture, the one Python forward of the graph, whose
+    # output tensor every replay rewrites (replays never call the hook).
+    last_out = []
+
+    def keep_outputs(_mod, _inp, out):
+        last_out[:] = [o.detach() for o in (out if isinstance(out, (tuple, list)) else (out,))]
+
     train_obj_pose = hasattr(model, "object_name")     # the reference's own switch (util/learn_utils.py:58)
     mk = lambda: M.PoseDistanceLoss(distance_metric="combined", scale_factor=1.0, alpha=0.5, mode="pose")
     criterion = {"obj_loss": mk(), "x0_loss": mk(), "x1_loss": mk(), "val_loss": M.PoseDistanceLoss(mode="val")}
@@ -205,6 +269,8 @@ def main():
     precondition_steps = 0
     if use_graph:
         # the whole step as ONE captured hipGraph (forward, loss, val metrics, backward on both streams, Adam); replayed per step
+        if args.dump_outputs:
+            model.register_forward_hook(keep_outputs)
         graphed = GraphedTrainStep(model, criterion, opt, train_obj_pose, batch, warmup=min(3, max(1, args.warmup)))
         batch = graphed.static
         run_step = lambda: graphed(batch)
@@ -219,6 +285,9 @@ def main():
         # PRECONDITION_QUIET_S seconds (at most PRECONDITION_MAX_S): clocks, caches and the allocator settle within the first two windows
         # (33 -> 19.6 ms/step).  The window times go to stderr; `precondition_s` is reported in the line.  (The "first process on a box is
         # 10-25 % slow" of this round's early A/B records was NOT the device: see the warm-up loop below.)
+        # The windows take a time-based number of optimizer steps, so the seeded state is restored after them: the W + N steps that
+        # follow (final_loss, --dump-outputs) are the same in every run with the same arguments.
+        pristine = snapshot_state(model, opt)
         t_pre, best, t_best = time.perf_counter(), None, None
         while True:
             t_w = time.perf_counter()
@@ -240,6 +309,8 @@ def main():
             if stop:
                 break
         precondition_s = time.perf_counter() - t_pre
+        restore_state(model, opt, pristine)
+        del pristine
         # the W warm-up steps run EXACTLY the statements of the timed loop -- incl. the NaN test of the loss value: its two small
         # kernels are loaded on first use (hipModuleLoad of the host framework's code object: ~10 ms in a process on a warm box, ~60 ms
         # in the first process after the box was leased or the repository copied), which inside a 20-step timed region read as
@@ -247,7 +318,7 @@ def main():
         # contain those statements, ran at full speed in the same process: profiles/r03_bench_first_process.txt)
         warm_flags = torch.zeros(max(1, args.warmup), dtype=torch.bool, device=dev)
         for i in range(args.warmup):
-            loss, _, _ = run_step()
+            loss, pos_err, ori_err = run_step()
             warm_flags[i] = loss != loss
 
     def fence():
@@ -258,9 +329,12 @@ def main():
     log("[bench] warm-up done; timing %d steps" % args.steps)
     fence()
     nan_flags = torch.zeros(args.steps, dtype=torch.bool, device=dev)   # NaN loss VALUES (see loss_note), tested on the device: no sync in the loop
+    hook_at = args.steps - 1 if args.dump_outputs and not use_graph else -1
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss, _, _ = run_step()
+        if i == hook_at:
+            model.register_forward_hook(keep_outputs)
+        loss, pos_err, ori_err = run_step()
         nan_flags[i] = loss != loss
     host_loop_ms = (time.perf_counter() - t0) / args.steps * 1e3   # host time per step INSIDE the free-running loop (see host_issue_ms below)
     fence()
@@ -282,89 +356,93 @@ def main():
                      "tests/golden/model_no_nanloss.npz); gradients and parameters finite" % (nan_loss_steps, args.steps))
 
     log("[bench] timed region: %.1f ms/step" % (dt / args.steps * 1e3))
-    # What the HOST needs to issue one step, measured on ISOLATED steps (outside the timed region): each starts with the device idle and
-    # is timed until its last call has returned, so the host never waits for the device.  The per-step host time inside the free-running
-    # timed loop (host_loop_ms_per_step) is NOT that: the HIP runtime lets a process run only a few steps ahead of the device (its
-    # kernel-argument / signal pools are bounded: the loop's host time follows the device time at a fixed distance -- round 4 measured
-    # 15.0 -> 14.1 ms when the DEVICE step went 19.24 -> 18.91 ms, profiles/r04_ab_t_gemm_off_chain.txt), so round 3's 12.3 ms was mostly waiting.
-    iso = []
-    for _ in range(5):
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, (loss, pos_err, ori_err), last_out)
+    host_issue_ms, roofline = None, None
+    if args.full:
+        # What the HOST needs to issue one step, measured on ISOLATED steps (outside the timed region): each starts with the device idle and
+        # is timed until its last call has returned, so the host never waits for the device.  The per-step host time inside the free-running
+        # timed loop (host_loop_ms_per_step) is NOT that: the HIP runtime lets a process run only a few steps ahead of the device (its
+        # kernel-argument / signal pools are bounded: the loop's host time follows the device time at a fixed distance -- round 4 measured
+        # 15.0 -> 14.1 ms when the DEVICE step went 19.24 -> 18.91 ms, profiles/r04_ab_t_gemm_off_chain.txt), so round 3's 12.3 ms was mostly waiting.
+        iso = []
+        for _ in range(5):
+            fence()
+            t1 = time.perf_counter()
+            run_step()
+            iso.append((time.perf_counter() - t1) * 1e3)
         fence()
-        t1 = time.perf_counter()
-        run_step()
-        iso.append((time.perf_counter() - t1) * 1e3)
-    fence()
-    host_issue_ms = sorted(iso)[len(iso) // 2]
+        host_issue_ms = sorted(iso)[len(iso) // 2]
+        # ---- profiled pass (not timed): HIP events around every launch of the trunk plan, per kernel family ----
+        plan = model.trunk._active
+        n_prof = 3
+        lib.rpe_resnet50_profile(plan.handle, 1)
+        for _ in range(n_prof):
+            train_step(model, batch, criterion, opt, train_obj_pose, "train", sync)
+        torch.cuda.synchronize()
+        ms = (ctypes.c_float * 6)()
+        launches = (ctypes.c_int * 6)()
+        flops = (ctypes.c_double * 6)()
+        byts = (ctypes.c_double * 6)()
+        lib.rpe_resnet50_profile_read(plan.handle, ms, launches, flops, byts)
+        log("[bench] profiled pass read back")
+        fam = {}
+        for i, c in enumerate(CATS):
+            if launches[i]:
+                fam[c] = {"ms_per_step": ms[i] / n_prof, "launches_per_step": launches[i] // n_prof,
+                          "tflops": (flops[i] / 1e12) / (ms[i] / n_prof / 1e3) if flops[i] else None,
+                          "gbs": (byts[i] / 1e9) / (ms[i] / n_prof / 1e3) if byts[i] else None}
+        # the same spans per kernel SYMBOL (names as rocprofv3 lists them, short form): the roofline line is for the symbol with
+        # the largest summed time; achieved = its algorithmic FLOPs per launch / its average launch duration
+        buf = ctypes.create_string_buffer(1 << 16)
+        nbytes = lib.rpe_resnet50_profile_kernels(plan.handle, buf, len(buf))
+        syms = []
+        for line in buf.raw[:max(0, nbytes)].decode().splitlines():
+            name, cnt, tms, fl, by = line.split(";")
+            syms.append({"kernel": name, "launches": int(cnt), "ms": float(tms), "flops": float(fl), "bytes": float(by)})
+        lib.rpe_resnet50_profile(plan.handle, 0)
+        dom = max(syms, key=lambda k: k["ms"])   # over EVERY profiled symbol of the trunk plan (GEMMs, BN / pooling passes, packing)
+        avg_ms = dom["ms"] / dom["launches"]
+        tflops = dom["flops"] / dom["launches"] / 1e12 / (avg_ms / 1e3)   # (0 for a pure streaming kernel)
+        gbs = dom["bytes"] / dom["launches"] / 1e9 / (avg_ms / 1e3)
+        # which roof bounds this kernel: arithmetic intensity against the ridge peak_flops / peak_bytes
+        ai = dom["flops"] / max(dom["bytes"], 1.0)
+        hbm_bound = dom["flops"] <= 0 or ai < PEAK_TFLOPS[args.dtype] * 1e12 / (PEAK_HBM_GBS * 1e9)
+        traffic, traffic_source = None, None
+        build_id = lib.rpe_build_id().decode()   # hash of the sources the LOADED library was built from (compiled into it)
+        tpath = os.path.join(ROOT, "profiles", "hbm_traffic_pmc.json")
+        if os.path.exists(tpath):  # PMC pass (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE) of this same command, committed per round
+            tj = json.load(open(tpath))
+            if tj.get("build_id") != build_id:
+                # the counters were collected on another build of the library: no number is better than a number about different kernels
+                traffic_source = "profiles/hbm_traffic_pmc.json was measured on build %s, this process loaded build %s: traffic withheld" % (tj.get("build_id"), build_id)
+            else:
+                for k in tj.get("kernels", []):
+                    if k["kernel"] == dom["kernel"]:
+                        traffic = round(k["per_launch_MB"] * 1e6)
+                        traffic_source = ("lookup in profiles/hbm_traffic_pmc.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on build %s = the library "
+                                          "this process loaded; NOT measured by this run)" % build_id)
+        roofline = {"bound": "hbm" if hbm_bound else "mfma", "kernel": dom["kernel"],
+                    "achieved": round(gbs if hbm_bound else tflops, 2), "peak": PEAK_HBM_GBS if hbm_bound else PEAK_TFLOPS[args.dtype],
+                    "unit": "GB/s" if hbm_bound else "TFLOP/s",
+                    "frac": round((gbs / PEAK_HBM_GBS) if hbm_bound else (tflops / PEAK_TFLOPS[args.dtype]), 4), "traffic": traffic, "traffic_source": traffic_source,
+                    "build_id": build_id,
+                    "avg_launch_ms": round(avg_ms, 4), "launches_per_step": dom["launches"] // n_prof,
+                    "algorithmic_mb_per_launch": round(dom["bytes"] / dom["launches"] / 1e6, 2),
+                    "algorithmic_gflop_per_launch": round(dom["flops"] / dom["launches"] / 1e9, 2),
+                    "arithmetic_intensity": round(ai, 1), "tflops": round(tflops, 1), "gbs": round(gbs, 1),
+                    # weight-gradient launches run on the engine's second stream beside the data-gradient / BN chain of the caller's
+                    # stream: their duration (and the chain's) is measured while the two share HBM and the CUs
+                    "stream": "second (beside the data-gradient chain)" if dom["kernel"].startswith("tn_kernel") else "caller's",
+                    "kernels": sorted(({"kernel": k["kernel"], "launches_per_step": k["launches"] // n_prof, "ms_per_step": round(k["ms"] / n_prof, 3),
+                                        "tflops": round(k["flops"] / 1e12 / (k["ms"] / 1e3), 1) if k["flops"] else None,
+                                        "gbs": round(k["bytes"] / 1e9 / (k["ms"] / 1e3), 1) if k["bytes"] else None} for k in syms),
+                                      key=lambda k: -k["ms_per_step"])[:int(os.environ.get("RPE_BENCH_TOPK", "8"))],
+                    "families": {k: {kk: (round(vv, 3) if isinstance(vv, float) else vv) for kk, vv in v.items()} for k, v in fam.items()}}
     if world > 1:   # the slowest rank's host is the one that matters
-        th = torch.tensor([host_issue_ms, host_loop_ms], dtype=torch.float64, device=dev)
+        th = torch.tensor([host_issue_ms or 0.0, host_loop_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(th, op=dist.ReduceOp.MAX)
-        host_issue_ms, host_loop_ms = th[0].item(), th[1].item()
-    # ---- profiled pass (not timed): HIP events around every launch of the trunk plan, per kernel family ----
-    plan = model.trunk._active
-    n_prof = 3
-    lib.rpe_resnet50_profile(plan.handle, 1)
-    for _ in range(n_prof):
-        train_step(model, batch, criterion, opt, train_obj_pose, "train", sync)
-    torch.cuda.synchronize()
-    ms = (ctypes.c_float * 6)()
-    launches = (ctypes.c_int * 6)()
-    flops = (ctypes.c_double * 6)()
-    byts = (ctypes.c_double * 6)()
-    lib.rpe_resnet50_profile_read(plan.handle, ms, launches, flops, byts)
-    log("[bench] profiled pass read back")
-    fam = {}
-    for i, c in enumerate(CATS):
-        if launches[i]:
-            fam[c] = {"ms_per_step": ms[i] / n_prof, "launches_per_step": launches[i] // n_prof,
-                      "tflops": (flops[i] / 1e12) / (ms[i] / n_prof / 1e3) if flops[i] else None,
-                      "gbs": (byts[i] / 1e9) / (ms[i] / n_prof / 1e3) if byts[i] else None}
-    # the same spans per kernel SYMBOL (names as rocprofv3 lists them, short form): the roofline line is for the symbol with
-    # the largest summed time; achieved = its algorithmic FLOPs per launch / its average launch duration
-    buf = ctypes.create_string_buffer(1 << 16)
-    nbytes = lib.rpe_resnet50_profile_kernels(plan.handle, buf, len(buf))
-    syms = []
-    for line in buf.raw[:max(0, nbytes)].decode().splitlines():
-        name, cnt, tms, fl, by = line.split(";")
-        syms.append({"kernel": name, "launches": int(cnt), "ms": float(tms), "flops": float(fl), "bytes": float(by)})
-    lib.rpe_resnet50_profile(plan.handle, 0)
-    dom = max(syms, key=lambda k: k["ms"])   # over EVERY profiled symbol of the trunk plan (GEMMs, BN / pooling passes, packing)
-    avg_ms = dom["ms"] / dom["launches"]
-    tflops = dom["flops"] / dom["launches"] / 1e12 / (avg_ms / 1e3)   # (0 for a pure streaming kernel)
-    gbs = dom["bytes"] / dom["launches"] / 1e9 / (avg_ms / 1e3)
-    # which roof bounds this kernel: arithmetic intensity against the ridge peak_flops / peak_bytes
-    ai = dom["flops"] / max(dom["bytes"], 1.0)
-    hbm_bound = dom["flops"] <= 0 or ai < PEAK_TFLOPS[args.dtype] * 1e12 / (PEAK_HBM_GBS * 1e9)
-    traffic, traffic_source = None, None
-    build_id = lib.rpe_build_id().decode()   # hash of the sources the LOADED library was built from (compiled into it)
-    tpath = os.path.join(ROOT, "profiles", "hbm_traffic_pmc.json")
-    if os.path.exists(tpath):  # PMC pass (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE) of this same command, committed per round
-        tj = json.load(open(tpath))
-        if tj.get("build_id") != build_id:
-            # the counters were collected on another build of the library: no number is better than a number about different kernels
-            traffic_source = "profiles/hbm_traffic_pmc.json was measured on build %s, this process loaded build %s: traffic withheld" % (tj.get("build_id"), build_id)
-        else:
-            for k in tj.get("kernels", []):
-                if k["kernel"] == dom["kernel"]:
-                    traffic = round(k["per_launch_MB"] * 1e6)
-                    traffic_source = ("lookup in profiles/hbm_traffic_pmc.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command on build %s = the library "
-                                      "this process loaded; NOT measured by this run)" % build_id)
-    roofline = {"bound": "hbm" if hbm_bound else "mfma", "kernel": dom["kernel"],
-                "achieved": round(gbs if hbm_bound else tflops, 2), "peak": PEAK_HBM_GBS if hbm_bound else PEAK_TFLOPS[args.dtype],
-                "unit": "GB/s" if hbm_bound else "TFLOP/s",
-                "frac": round((gbs / PEAK_HBM_GBS) if hbm_bound else (tflops / PEAK_TFLOPS[args.dtype]), 4), "traffic": traffic, "traffic_source": traffic_source,
-                "build_id": build_id,
-                "avg_launch_ms": round(avg_ms, 4), "launches_per_step": dom["launches"] // n_prof,
-                "algorithmic_mb_per_launch": round(dom["bytes"] / dom["launches"] / 1e6, 2),
-                "algorithmic_gflop_per_launch": round(dom["flops"] / dom["launches"] / 1e9, 2),
-                "arithmetic_intensity": round(ai, 1), "tflops": round(tflops, 1), "gbs": round(gbs, 1),
-                # weight-gradient launches run on the engine's second stream beside the data-gradient / BN chain of the caller's
-                # stream: their duration (and the chain's) is measured while the two share HBM and the CUs
-                "stream": "second (beside the data-gradient chain)" if dom["kernel"].startswith("tn_kernel") else "caller's",
-                "kernels": sorted(({"kernel": k["kernel"], "launches_per_step": k["launches"] // n_prof, "ms_per_step": round(k["ms"] / n_prof, 3),
-                                    "tflops": round(k["flops"] / 1e12 / (k["ms"] / 1e3), 1) if k["flops"] else None,
-                                    "gbs": round(k["bytes"] / 1e9 / (k["ms"] / 1e3), 1) if k["bytes"] else None} for k in syms),
-                                  key=lambda k: -k["ms_per_step"])[:int(os.environ.get("RPE_BENCH_TOPK", "8"))],
-                "families": {k: {kk: (round(vv, 3) if isinstance(vv, float) else vv) for kk, vv in v.items()} for k, v in fam.items()}}
+        host_issue_ms, host_loop_ms = th[0].item() if args.full else None, th[1].item()
 
     if rank == 0:
         imgs = args.batch * world * args.steps
@@ -372,19 +450,22 @@ def main():
             "metric": "images/sec (train step, 224x224 bs256 per GPU)", "value": round(imgs / dt, 2), "unit": "images/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": args.dtype, "data": "synthetic",
-            # optimizer steps taken on the synthetic batch BEFORE the W warm-up steps (untimed 10-step windows): final_loss / nan_loss_steps
-            # describe the state after precondition_steps + warmup + steps updates.  The timed loop's statements are `run_step()` and the
-            # device-side NaN test of the loss value (two small elementwise launches per step, inside the timed region since round 3).
+            # optimizer steps taken on the synthetic batch BEFORE the W warm-up steps (untimed 10-step windows, after which the seeded state
+            # is restored): final_loss / nan_loss_steps describe the state after warmup + steps updates.  The timed loop's statements are
+            # `run_step()` and the device-side NaN test of the loss value (two small elementwise launches per step, inside the timed region
+            # since round 3).
             "precondition_s": round(precondition_s, 2), "precondition_steps": precondition_steps,
-            "host_issue_ms_per_step": round(host_issue_ms, 2), "host_loop_ms_per_step": round(host_loop_ms, 2),
+            "host_loop_ms_per_step": round(host_loop_ms, 2),
             "config": {"workload": (workloads[args.model] if args.resnet == 50 else workloads[args.model].replace("ResNet-50", "ResNet-%d" % args.resnet).replace("BASELINE.json ", "as BASELINE.json ")) +
                                    (" [use_depth=True]" if dh else ""), "model": args.model,
                        "images_per_gpu": args.batch, "global_batch": args.batch * world, "resolution": 224, "latent_dim": 512,
                        "parallelism": "dp%d" % world + (" (RCCL world 1: staged joins + bucketed all-reduce on one GPU)" if args.force_dist else ""),
                        "launch": "hipGraph replay" if use_graph else "eager", "final_loss": final_loss, "nan_loss_steps": nan_loss_steps,
                        "loss_note": loss_note, "params_finite": params_finite},
-            "roofline": roofline,
         }
+        if args.full:
+            out["host_issue_ms_per_step"] = round(host_issue_ms, 2)
+            out["roofline"] = roofline
         # whole-step view against both roofs (24.52 GFLOP and 152.9 MB per image)
         ips = imgs / dt / world
         out["step_roofline"] = {"tflops_per_gpu": round(ips * 24.52e9 / 1e12, 2), "frac_mfma": round(ips * 24.52e9 / 1e12 / PEAK_TFLOPS[args.dtype], 4),
@@ -392,7 +473,7 @@ def main():
         if args.resnet != 50:   # a side record: the per-image constants above and the metric are the ResNet-50 workload's
             out.pop("step_roofline")
             out["metric"] += " [side record: ResNet-%d trunk, not the BASELINE workload]" % args.resnet
-        if world == 1 and not args.no_cpu_baseline and args.model == "no" and not dh and not args.force_dist and args.resnet == 50:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model == "no" and not dh and not args.force_dist and args.resnet == 50:
             out["cpu_baseline"], ref_first = cpu_baseline()
             del model, opt
             torch.cuda.empty_cache()

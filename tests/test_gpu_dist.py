@@ -185,7 +185,7 @@ def test_bench_data_parallel_path_host_stays_ahead_of_the_device():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--steps", "6", "--warmup", "2", "--batch", "128", "--no-cpu-baseline", "--precondition-min", "1"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--force-dist", "--full", "--steps", "6", "--warmup", "2", "--batch", "128", "--no-cpu-baseline", "--precondition-min", "1"]
     r = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

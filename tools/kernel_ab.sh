@@ -6,7 +6,7 @@ out=gpurun_out/kernel_ab.txt
 for cfg in "$@"; do
   echo "== $cfg" >> $out
   if [ "$cfg" = "-" ]; then e="RPE_AB=none"; else e="$cfg"; fi
-  env $e RPE_BENCH_TOPK=80 timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --precondition-min 2 2>/dev/null | python -c "
+  env $e RPE_BENCH_TOPK=80 timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --precondition-min 2 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('ms_per_step', d['ms_per_step'])

@@ -14,7 +14,7 @@ mkdir -p $out
 hb=$!
 trap "kill $hb 2>/dev/null" EXIT
 has() { case " $phases " in *" $1 "*) return 0;; *) return 1;; esac; }
-B="--steps 2 --warmup 1 --no-cpu-baseline --precondition-min 2"
+B="--full --steps 2 --warmup 1 --no-cpu-baseline --precondition-min 2"
 cd /tmp && export TMPDIR=/tmp
 if has pmc; then
   timeout -k 10 400 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc -o fetch -- python3 $root/bench.py $B > /dev/null 2> $out/fetch.err || echo "fetch pass failed" >> $out/progress.txt
@@ -31,25 +31,25 @@ if has mfma; then
   rm -rf $out/mfma
 fi
 if has stats; then
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o st -- python3 $root/bench.py --steps 5 --warmup 2 --no-cpu-baseline --precondition-min 2 > $out/bench_under_rocprof.json 2> $out/stats.err
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o st -- python3 $root/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --precondition-min 2 > $out/bench_under_rocprof.json 2> $out/stats.err
   (cd $root && python tools/timeline.py $out/stats/st_kernel_trace.csv -5 > $out/timeline.txt)
   rm -f $out/stats/*.db $out/stats/st_kernel_trace.csv   # (the raw trace is tens of MB; gpurun merges at most 64 MiB back)
   echo "stats done" >> $out/progress.txt
 fi
 cd $root
 if has bench; then
-  python bench.py > $out/bench.json 2> $out/bench.err
+  python bench.py --full > $out/bench.json 2> $out/bench.err
   echo "bench done" >> $out/progress.txt
 fi
 if has models; then
-  for m in n td tdo_v2; do python bench.py --model $m --steps 20 --warmup 5 --no-cpu-baseline --precondition-min 2 2>> $out/models.err | tail -1 > $out/bench_model_$m.json; done
-  python bench.py --model tdo --depth-head --steps 20 --warmup 5 --no-cpu-baseline --precondition-min 2 2>> $out/models.err | tail -1 > $out/bench_model_tdo_depth.json
-  python bench.py --dtype f16 --steps 30 --warmup 8 --no-cpu-baseline --precondition-min 2 2>> $out/models.err | tail -1 > $out/bench_f16.json
+  for m in n td tdo_v2; do python bench.py --full --model $m --steps 20 --warmup 5 --no-cpu-baseline --precondition-min 2 2>> $out/models.err | tail -1 > $out/bench_model_$m.json; done
+  python bench.py --full --model tdo --depth-head --steps 20 --warmup 5 --no-cpu-baseline --precondition-min 2 2>> $out/models.err | tail -1 > $out/bench_model_tdo_depth.json
+  python bench.py --full --dtype f16 --steps 30 --warmup 8 --no-cpu-baseline --precondition-min 2 2>> $out/models.err | tail -1 > $out/bench_f16.json
   echo "models done" >> $out/progress.txt
 fi
 if has dist; then
-  python bench.py --force-dist --steps 30 --warmup 8 --no-cpu-baseline --precondition-min 2 2>> $out/dist.err | tail -1 > $out/bench_force_dist.json
-  python bench.py --steps 30 --warmup 8 --no-cpu-baseline --precondition-min 2 2>> $out/dist.err | tail -1 > $out/bench_plain_same_box.json
+  python bench.py --full --force-dist --steps 30 --warmup 8 --no-cpu-baseline --precondition-min 2 2>> $out/dist.err | tail -1 > $out/bench_force_dist.json
+  python bench.py --full --steps 30 --warmup 8 --no-cpu-baseline --precondition-min 2 2>> $out/dist.err | tail -1 > $out/bench_plain_same_box.json
   echo "dist done" >> $out/progress.txt
 fi
 if has loss; then   # (minutes of host time: the convergence records are usually run on their own, tools/loss_record.py 256 300 0 fresh)

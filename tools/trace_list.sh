@@ -7,7 +7,7 @@ case $out in /*) ;; *) out=$root/$out ;; esac
 shift || true
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $out/tr -o st -- python3 $root/bench.py --steps 5 --warmup 2 --no-cpu-baseline --precondition-min 2 "$@" > $out/bench.json 2> $out/bench.err
+rocprofv3 --kernel-trace --output-format csv -d $out/tr -o st -- python3 $root/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --precondition-min 2 "$@" > $out/bench.json 2> $out/bench.err
 cd $root
 python tools/timeline.py $out/tr/st_kernel_trace.csv -5 --list > $out/list.txt
 rm -rf $out/tr
