@@ -1,12 +1,17 @@
 """GPU parity of every C-ABI kernel against a CPU fp32 torch statement of the same op (and the
 oracle where it has one).  Tolerances: fp32 path 2e-5 of the reference's max magnitude (exact-fp32
-MFMA, different summation order); bf16 path 2e-2 (8-bit mantissa inputs, fp32 accumulation); fp16 path 3e-3 (11 bits)."""
+MFMA, different summation order); bf16 path 2e-2 (8-bit mantissa inputs, fp32 accumulation); fp16 path 3e-3 (11 bits).
+The GEMM-family kernels are held, besides, to the element-wise bound of tests/_bounds.py (fp32 accumulation + one rounding into
+the output type, against an fp64 reference built on the device from the same operands) and, for 16-bit outputs, to unbiased
+rounding."""
 import os
 
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+
+import _bounds as B
 
 pytestmark = pytest.mark.gpu
 
@@ -43,6 +48,20 @@ def nchw(t):
     return t.permute(0, 3, 1, 2).contiguous()
 
 
+def dd(t):
+    """an operand of an fp64 bound reference, on the device"""
+    return t.detach().to(DEV, torch.float64)
+
+
+def within(got, r, dtype, label, out=None, gain=1.0, epi=None, layout=None):
+    """got (kernel output, stored in dtype) against the fp64 reference r (+ epilogue): element-wise bound and rounding bias"""
+    ref = r.acc if out is None else out
+    bnd = B.bound(r, dtype, out=ref, gain=gain, epi=epi)
+    B.assert_within(got, ref, bnd, label, layout)
+    B.assert_unbiased(got, ref, dtype, label, bnd)
+    B.assert_rounds_once(got, ref, dtype, label, bnd)
+
+
 # ------------------------------------------------------------------ dense GEMM (MFMA layout check)
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("m,n,k", [(200, 7, 36), (128, 128, 64), (300, 130, 200), (64, 70, 8), (1, 512, 2048), (5000, 130, 1032), (4100, 40, 1024)])
@@ -58,6 +77,8 @@ def test_linear_fwd_layout(dtype, m, n, k):
     out = ops.linear_fwd(xd, wd, b.to(DEV), relu=True)
     ref = F.relu(q(x, dtype) @ q(w, dtype).t() + b)
     assert rel_err(out, ref) < tol(dtype)
+    r, b64 = B.linear_ref(dd(q(x, dtype)), dd(q(w, dtype))), dd(b)
+    within(out, r, dtype, "linear_fwd tile %s" % (dtype,), out=F.relu(r.acc + b64), epi=r.acc.abs() + b64.abs())
 
 
 @pytest.mark.parametrize("m,n,k", [(1, 1024, 3655), (1, 7, 64), (2, 130, 259), (3, 64, 1000), (5, 33, 4099), (8, 512, 2048), (7, 9, 1)])
@@ -72,8 +93,11 @@ def test_linear_fwd_few_rows(m, n, k):
     ref = x.double() @ w.double().t() + b.double()
     out = ops.linear_fwd(xd, wd, b.to(DEV))
     assert rel_err(out, ref.float()) < 2e-6
+    r, b64, add64 = B.linear_ref(dd(x), dd(w)), dd(b), dd(add)
+    within(ops.linear_fwd(xd, wd, b.to(DEV)), r, torch.float32, "linear_fwd few-row", out=r.acc + b64, epi=r.acc.abs() + b64.abs())
     out = ops.linear_fwd(xd, wd, b.to(DEV), relu=True, addend=ad)
     assert rel_err(out, F.relu(ref + add.double()).float()) < 2e-6
+    within(out, r, torch.float32, "linear_fwd few-row +addend", out=F.relu(r.acc + b64 + add64), epi=r.acc.abs() + b64.abs() + add64.abs())
     out = ops.linear_fwd(xd, wd, None)
     assert rel_err(out, (ref - b.double()).float()) < 2e-6
     # the same product through the MFMA tile kernel (9 rows: one more than the few-row limit), row by row
@@ -101,6 +125,8 @@ def test_linear_fwd_split_k(m, n, k):
     assert "nt_split_epilogue_kernel" in ops.last_kernel_name()
     ref = F.relu(x.double() @ w.double().t() + b.double() + add.double()).float()
     assert rel_err(out, ref) < 2e-5
+    r, b64, add64 = B.linear_ref(dd(x), dd(w)), dd(b), dd(add)
+    within(out, r, torch.float32, "linear_fwd split-K", out=F.relu(r.acc + b64 + add64), epi=r.acc.abs() + b64.abs() + add64.abs())
     assert torch.equal(out, ops.linear_fwd(xd, wd, bd, relu=True, addend=ad[:, :n]))
     plain = ops.linear_fwd(xd, wd, bd)
     assert rel_err(plain, (x.double() @ w.double().t() + b.double()).float()) < 2e-5
@@ -119,11 +145,16 @@ def test_linear_wgrad(dtype, m, n, k):
     ops.linear_wgrad(dy.to(dtype).to(DEV), x.to(dtype).to(DEV), dw, n=n, k=kp)
     ref = q(dy, dtype)[:, :n].t() @ q(x, dtype)
     assert rel_err(dw, ref) < tol(dtype)
+    r = B.gemm_ref_tn(dd(q(dy, dtype)[:, :n]), dd(q(x, dtype)))           # fp32 output: no output rounding
+    within(dw, r, torch.float32, "linear_wgrad det %s" % (dtype,))
     ops.linear_wgrad(dy.to(dtype).to(DEV), x.to(dtype).to(DEV), dw, n=n, k=kp)        # accumulates: dw += ...
     assert rel_err(dw, 2 * ref) < tol(dtype)
+    r2 = B.Ref(2 * r.acc, 2 * r.Q, r.K)                                     # two sums and one fp32 add of them
+    within(dw, r2, torch.float32, "linear_wgrad accumulate %s" % (dtype,), epi=r2.acc.abs())
     dwa = torch.zeros(n, kp, device=DEV)
     ops.linear_wgrad(dy.to(dtype).to(DEV), x.to(dtype).to(DEV), dwa, n=n, k=kp, deterministic=False)
     assert rel_err(dwa, ref) < tol(dtype)
+    within(dwa, r, torch.float32, "linear_wgrad atomic %s" % (dtype,))
 
 
 # ------------------------------------------------------------------ convolution
@@ -172,6 +203,13 @@ def test_conv_fwd_and_stats(dtype, cfg):
     sums = st.sum(0).cpu()  # [2, Co]
     assert rel_err(sums[0], ref.sum((0, 2, 3))) < 1e-3 + tol(dtype)
     assert rel_err(sums[1], (ref * ref).sum((0, 2, 3))) < 1e-3 + tol(dtype)
+    r = B.conv_fwd_ref(dd(x), dd(w), s, p)
+    within(y, r, dtype, "conv_fwd %s %s" % (cfg, dtype))
+    check_stats(st, r, "conv_fwd stats %s %s" % (cfg, dtype))
+
+
+def check_stats(st, r, label):
+    B.assert_stats(st, r, label)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -188,6 +226,8 @@ def test_conv_dgrad(dtype, cfg):
     w_crsk = w.permute(1, 2, 3, 0).contiguous()  # [Ci, kh, kw, Co]
     dx = ops.conv2d_dgrad(nhwc(dy).to(dtype).to(DEV), w_crsk.to(dtype).to(DEV), (b, h, h, ci), s, p, addend=nhwc(add).to(dtype).to(DEV))
     assert rel_err(nchw(dx), ref + add) < tol(dtype)
+    r, a64 = B.conv_dgrad_ref(dd(dy), dd(w), (h, h), s, p), dd(nhwc(add))
+    within(dx, r, dtype, "conv_dgrad +addend %s %s" % (cfg, dtype), out=r.acc + a64, epi=r.acc.abs() + a64.abs())
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -202,9 +242,12 @@ def test_conv_wgrad(dtype, cfg):
     xd, dyd = nhwc(x).to(dtype).to(DEV), nhwc(dy).to(dtype).to(DEV)
     dw = ops.conv2d_wgrad(xd, dyd, k, s, p)                      # slab + fixed-order sum
     assert rel_err(dw.permute(0, 3, 1, 2), ref) < tol(dtype)
+    r = B.conv_wgrad_ref(dd(x), dd(dy), k, s, p)
+    within(dw, r, torch.float32, "conv_wgrad det %s %s" % (cfg, dtype), layout="krsc")
     assert torch.equal(dw, ops.conv2d_wgrad(xd, dyd, k, s, p)), "the deterministic weight gradient is not bitwise reproducible"
     dwa = ops.conv2d_wgrad(xd, dyd, k, s, p, deterministic=False)   # fp32 atomics
     assert rel_err(dwa.permute(0, 3, 1, 2), ref) < tol(dtype)
+    within(dwa, r, torch.float32, "conv_wgrad atomic %s %s" % (cfg, dtype), layout="krsc")
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
@@ -454,10 +497,15 @@ def test_stem_conv(dtype):
     y, st = ops.stem_conv_fwd(x4, wp, want_stats=True)
     assert rel_err(nchw(y), ref) < tol(dtype)
     assert rel_err(st.sum(0)[0], ref.sum((0, 2, 3))) < 1e-3 + tol(dtype)
+    r = B.conv_fwd_ref(dd(img), dd(w), 2, 3)
+    within(y, r, dtype, "stem_fwd %s" % (dtype,))
+    check_stats(st, r, "stem_fwd stats %s" % (dtype,))
     dy = q(torch.randn(ref.shape, generator=g), dtype)
     (dw_ref,) = torch.autograd.grad(ref, w, dy)
     dw = ops.stem_conv_wgrad(x4, nhwc(dy).to(dtype).to(DEV))
     assert rel_err(dw, dw_ref) < tol(dtype)
+    r = B.conv_wgrad_ref(dd(img), dd(dy), 7, 2, 3)                          # [64, 7, 7, 3]; the kernel's layout is [64, 3, 7, 7]
+    within(dw.reshape(64, 3, 7, 7).permute(0, 2, 3, 1), r, torch.float32, "stem_wgrad %s" % (dtype,), layout="krsc")
 
 
 # ------------------------------------------------------------------ batch norm / pooling
@@ -816,6 +864,10 @@ def test_conv_fwd_affine_inference_form(dtype, cfg, residual):
     out = ops.conv2d_fwd_affine(nhwc(x).to(dtype).to(DEV), wq.permute(0, 2, 3, 1).contiguous().to(dtype).to(DEV), s, p, shift.to(DEV),
                                 None if add is None else nhwc(add).to(dtype).to(DEV), True)
     assert rel_err(nchw(out), ref) < tol(dtype)
+    r, sh64 = B.conv_fwd_ref(dd(x), dd(wq), s, p), dd(shift)
+    a64 = 0.0 if add is None else dd(nhwc(add))
+    within(out, r, dtype, "conv_fwd_affine %s res=%s %s" % (cfg, residual, dtype), out=F.relu(r.acc + sh64 + a64),
+           epi=r.acc.abs() + sh64.abs() + (a64.abs() if add is not None else 0.0))
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
@@ -861,9 +913,11 @@ def test_conv1x1_forward_with_bn_from_gram(dtype, cfg, shortcut):
     S, s1, buf = ops.gram(xd)
     assert rel_err(S, (x.reshape(rows, ci).double().t() @ x.reshape(rows, ci).double()).float()) < 2e-5
     assert rel_err(s1, x.reshape(rows, ci).double().sum(0).float()) < 2e-5
+    check_gram(S, s1, dd(x.reshape(rows, ci)), "gram %s %s" % (cfg, dtype))
     assert torch.equal(buf, ops.gram(xd)[2])                                          # fixed-order sums
     rm, rv = torch.zeros(co, device=DEV), torch.ones(co, device=DEV)
     scale, shift, mean, invstd = ops.bn_stats_from_gram(wd, buf, rows, gamma.to(DEV), beta.to(DEV), rm, rv)
+    B.assert_gram_stats((scale, shift, mean, invstd), dd(x.reshape(rows, ci)), dd(w), dd(gamma), dd(beta), "bn_stats_from_gram %s %s" % (cfg, dtype))
     assert rel_err(mean, mean_ref.float()) < 1e-4
     assert ((invstd.cpu().double() * torch.sqrt(var_ref + 1e-5) - 1).abs().max()) < 2e-4
     assert rel_err(rm, 0.1 * mean_ref.float()) < 1e-4
@@ -882,11 +936,23 @@ def test_conv1x1_forward_with_bn_from_gram(dtype, cfg, shortcut):
     out, mask, y = ops.conv1x1_fwd_bn(xd, wd, scale, shift, None if res is None else res.to(dtype).to(DEV).reshape(b, h, h, co), dev(rs), dev(rb), want_y=True)
     assert rel_err(out, ref) < tol(dtype)
     assert rel_err(y, y64.float().reshape(b, h, h, co)) < tol(dtype)
+    # element-wise: y against fp64; out against the kernel's own scale / shift (bn_stats_from_gram's outputs) applied in fp64
+    r = B.linear_ref(dd(x.reshape(rows, ci)), dd(w))
+    within(y.reshape(rows, co), r, dtype, "conv1x1_fwd_bn y %s %s" % (cfg, dtype))
+    sc64, sh64 = scale.double(), shift.double()
+    pre, epi = r.acc * sc64 + sh64, (r.acc * sc64).abs() + sh64.abs()
+    if res is not None:
+        rr = dd(res) * (dd(rs) if rs is not None else 1.0)
+        rbb = dd(rb) if rb is not None else torch.zeros((), dtype=torch.float64, device=DEV)
+        pre, epi = pre + rr + rbb, epi + rr.abs() + rbb.abs()
+    label = "conv1x1_fwd_bn out %s %s %s" % (cfg, shortcut, dtype)
+    within(out.reshape(rows, co), r, dtype, label + " tiled", out=F.relu(pre), gain=sc64, epi=epi)
     bits = ((mask.cpu()[:, None] >> torch.arange(8, dtype=torch.uint8)) & 1).reshape(rows, co).bool()
     assert torch.equal(bits, out.cpu().float().reshape(rows, co) > 0)
     # without y the 64 / 128 -> 256 k launches of >= 512 rows take the row-streaming kernel (csrc/stream1x1.hip; ragged spans in the (3, 30, ..)
     # and (5, 14, ..) cases): bitwise the tiled form, in both walk directions
     out2, mask2, none = ops.conv1x1_fwd_bn(xd, wd, scale, shift, None if res is None else res.to(dtype).to(DEV).reshape(b, h, h, co), dev(rs), dev(rb))
+    within(out2.reshape(rows, co), r, dtype, label + (" " + ops.last_kernel_name().split("<")[0]), out=F.relu(pre), gain=sc64, epi=epi)
     assert none is None and torch.equal(out2, out) and torch.equal(mask2, mask)
     if rows >= 512 and ci in (64, 128) and co % 256 == 0 and shortcut != "none":
         assert ops.last_kernel_name().startswith("conv1x1_stream_fwd_kernel")
@@ -896,6 +962,18 @@ def test_conv1x1_forward_with_bn_from_gram(dtype, cfg, shortcut):
     finally:
         ops.set_walk_direction(0)
     assert torch.equal(out3, out) and torch.equal(mask3, mask)
+
+
+def check_gram(S, s1, x64, label):
+    """Gram matrix S = x^T x and column sums s1 (fp32 outputs) against fp64, element-wise"""
+    B.assert_within(S, *_gram_ref(x64), label + " S")
+    r1 = B.Ref(x64.sum(0), (x64 * x64).sum(0).sqrt(), x64.shape[0])
+    B.assert_within(s1, r1.acc, B.bound(r1, torch.float32), label + " s1")
+
+
+def _gram_ref(x64):
+    r = B.gemm_ref_tn(x64, x64)
+    return r.acc, B.bound(r, torch.float32)
 
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
@@ -912,6 +990,7 @@ def test_bn_apply_fused_with_gram(dtype, rows, c):
     assert torch.equal(out, ref)
     a = out.double().cpu()
     assert rel_err(S, (a.t() @ a).float()) < 2e-5
+    check_gram(S, s1, dd(out), "bn_apply_gram %d x %d %s" % (rows, c, dtype))
     assert rel_err(s1, a.sum(0).float()) < 2e-5
     S2, s12, _ = ops.gram(out)
     assert rel_err(S, S2) < 2e-5 and rel_err(s1, s12) < 2e-5
@@ -966,6 +1045,11 @@ def test_y3_free_bottleneck_backward(dtype, cfg):
     assert rel_err(st[:, 0].sum(0), dz.float().reshape(rows, co).sum(0)) < 1e-5          # the sum of dz AS STORED (rounded), so that it is
     assert rel_err(st[:, 0].sum(0), st_y[:, 0].sum(0)) < t                              # consistent with T = dz^T a2 in (b)
     assert rel_err(dz.reshape(rows, co), dz_ref.float()) < t
+    # element-wise: dz = (dy1 W1 + shortcut gradient) o mask, the mask being the forward's own packed one
+    r = B.gemm_ref(dd(dy1), dd(w1n.t()))
+    bits64, sg64 = dd(bits), dd(sc_grad)
+    within(dz.reshape(rows, co), r, dtype, "conv2d_dgrad_bn masked %s %s" % (cfg, dtype), out=(r.acc + sg64) * bits64,
+           epi=r.acc.abs() + sg64.abs())
     # (a') the same launch with the T side product: identical dz and partial sums, T == the separate dz^T a2 launch (up to the fp32
     # summation order), repeatable bit for bit
     if p in (64, 128):
@@ -973,6 +1057,7 @@ def test_y3_free_bottleneck_backward(dtype, cfg):
         assert torch.equal(dz_t, dz) and torch.equal(st_t, st)
         assert rel_err(T_t, ops.conv2d_wgrad(a2d, dz, 1, 1, 0).reshape(co, p)) < 2e-5
         assert rel_err(T_t, (dz.double().cpu().reshape(rows, co).t() @ a2.double()).float()) < 2e-5
+        within(T_t, B.gemm_ref_tn(dd(dz.reshape(rows, co)), dd(a2)), torch.float32, "conv1x1_dgrad_bn_t T %s %s" % (cfg, dtype))
         assert torch.equal(T_t, ops.conv1x1_dgrad_bn_t(dyd, w_crsk, (b, h, h, co), a2d, mask, addend=add)[2])
     # (b)
     T = ops.conv2d_wgrad(a2d, dz, 1, 1, 0).reshape(co, p)
@@ -1066,6 +1151,8 @@ def test_conv_fwd_affine_split_k(dtype, cfg):
     out = ops.conv2d_fwd_affine(xd, wd, s, p, shift.to(DEV), ad, True)
     assert "nt_split_epilogue_kernel" in ops.last_kernel_name()
     assert rel_err(nchw(out), ref) < tol(dtype)
+    r, sh64, a64 = B.conv_fwd_ref(dd(x), dd(wq), s, p), dd(shift), dd(nhwc(add))
+    within(out, r, dtype, "conv_fwd_affine split-K %s %s" % (cfg, dtype), out=F.relu(r.acc + sh64 + a64), epi=r.acc.abs() + sh64.abs() + a64.abs())
     plain = ops.conv2d_fwd_affine(xd, wd, s, p, shift.to(DEV), ad, True, split_k=False)
     assert "nt_split_epilogue_kernel" not in ops.last_kernel_name()
     assert rel_err(out, plain) < (2e-6 if dtype == torch.float32 else tol(dtype))
@@ -1187,6 +1274,7 @@ def test_conv_wgrad_halo_form(dtype, cfg):
         dw = ops.conv2d_wgrad(xd, dyd, 3, 1, 1)
         assert ops.last_kernel_name().startswith("wgrad_halo"), ops.last_kernel_name()
         assert rel_err(dw.permute(0, 3, 1, 2), ref) < tol(dtype)
+        within(dw, B.conv_wgrad_ref(dd(x), dd(dy), 3, 1, 1), torch.float32, "wgrad_halo %s %s" % (cfg, dtype), layout="krsc")
         assert torch.equal(dw, ops.conv2d_wgrad(xd, dyd, 3, 1, 1)), "the halo-form weight gradient is not bitwise reproducible"
         lib.rpe_conv2d_wgrad_halo_min_width(1000)
         dwg = ops.conv2d_wgrad(xd, dyd, 3, 1, 1)
