@@ -345,6 +345,23 @@ int rpe_depth_head_fwd_pools(const float* depth, const float* w, const float* b,
 /* dst += src over n elements of the compute dtype (n a multiple of the 16-byte chunk) */
 int rpe_tensor_add(int dtype, void* dst, const void* src, long n, void* stream);
 
+/* ------------------------------------------------------------------ layer capture */
+/* replaces: the forward hook of visualize_layer, `output.squeeze(dim=0).detach().numpy()` (util/model_utils.py:38-40), on the engine's
+ * buffers: image `image` of an NHWC activation x[..][H][W][C] in the compute dtype -> out[C][H][W] fp32 (the widening is exact) and,
+ * per channel, the minimum and maximum over its FINITE values, minmax[C][2] (+inf, -inf for a channel without one; -0 == +0).
+ * C a whole number of 16-byte chunks with x 16-byte aligned takes the vector path, any other C >= 1 element loads (the heads' [B][h*w]
+ * vectors are H = h, W = w, C = 1 maps).  _batch: all B images of the buffer in one launch, out[B][C][H][W], minmax[B][C][2]. */
+int rpe_feature_planes(int dtype, const void* x_nhwc, int image, int H, int W, int C, float* out_chw_f32, float* minmax, void* stream);
+int rpe_feature_planes_batch(int dtype, const void* x_nhwc, int B, int H, int W, int C, float* out_bchw_f32, float* minmax, void* stream);
+/* replaces: the subplot(n, n, i + 1) / imshow / invert_yaxis loop of visualize_layer (util/model_utils.py:88-104) up to the colour
+ * lookup: one uint8 colour-INDEX image of rows = ceil(C / cols) by cols tiles, tile c at cell (c / cols, c % cols), tile pitch
+ * (H + gutter, W + gutter), size rows (H + gutter) - gutter by cols (W + gutter) - gutter; gutter pixels and unused cells are 0.
+ * A pixel v of channel c with (lo, hi) = minmax[c]: t = (v - lo) / (hi - lo), index = min(255, (int)(t * 256)), every operation
+ * correctly rounded fp32 (matplotlib's Normalize + 256-entry lookup); hi == lo (a constant channel) or a non-finite v -> 0.
+ * flip_y: tile row r shows plane row H - 1 - r (invert_yaxis). */
+int rpe_feature_mosaic(const float* planes, const float* minmax, int C, int H, int W, int cols, int gutter, int flip_y, unsigned char* out_u8,
+                       void* stream);
+
 /* replaces: nn.Linear (+ F.relu) of the proprio-fusion MLP (models/naive.py:343-345), the
  * ResNet fc (util/model_utils.py:141), the LSTM input/recurrent GEMMs and the fc heads
  * (models/time_sensitive.py:420-423,510).  y[M][N] = x[M][K] w[N][K]^T (+bias) (+addend) (relu).

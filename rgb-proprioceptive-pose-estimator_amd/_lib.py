@@ -167,6 +167,9 @@ _SPEC = {
     "rpe_aux_head_bwd_c": (I, [I, P, L, P, I, P, P, P, P, P, P, P, P, I, I, I, P]),
     "rpe_depth_head_fwd_pools": (I, [P, P, P, P, P, I, I, I, I, P]),
     "rpe_tensor_add": (I, [I, P, P, L, P]),
+    "rpe_feature_planes": (I, [I, P, I, I, I, I, P, P, P]),
+    "rpe_feature_planes_batch": (I, [I, P, I, I, I, I, P, P, P]),
+    "rpe_feature_mosaic": (I, [P, P, I, I, I, I, I, I, P, P]),
 }
 # entry points whose int return value is data, not a status
 _NOT_STATUS = {"rpe_abi_version", "rpe_conv2d_wgrad_halo_min_width"}

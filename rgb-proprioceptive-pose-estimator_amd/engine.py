@@ -289,13 +289,16 @@ class _Plan:
 
     def hooked_feature(self, layer):
         """The tensor a forward hook on `layer` sees (models/naive.py:201-211): 0 conv1's raw output, 9 bn1 (after the in-place
-        ReLU), 1..3 the output of layerN -- NHWC, compute dtype, aliasing the workspace."""
+        ReLU), 1..4 the output of layerN -- NHWC, compute dtype, aliasing the workspace.  (Layer 4 is for capture only,
+        util.model_utils.capture_layer: the reference cannot hang an aux head on it, models/_core.py.)"""
         if layer == 9:
             return self.early_feature()
         if layer == 0:
             return self.tensor("conv1.y").view(self.batch, self.h // 2, self.w // 2, 64)
         t = self.tensor("layer%d.%d.%s.a" % (layer, _BLOCKS[self.trunk.depth][layer - 1] - 1, "conv2" if self.trunk.depth in _BASIC else "conv3"))
-        s = 2 << layer   # layer1: 1/4 of the image, layer2: 1/8, layer3: 1/16
+        if layer not in (1, 2, 3, 4):
+            raise ValueError("hooked_feature: layers 0 (conv1), 9 (bn1) and 1..4 exist; got %r" % (layer,))
+        s = 2 << layer   # layer1: 1/4 of the image, layer2: 1/8, layer3: 1/16, layer4: 1/32
         return t.view(self.batch, self.h // s, self.w // s, t.shape[1])
 
     def set_hook_grad(self, layer, dense):

@@ -250,6 +250,39 @@ class AuxHeadOp:
             self.saved = (plan, raw, idx, feat, xhat, b, h, w, n)
         return out_cols
 
+    def parts(self, plan, depth, which):
+        """After an INFERENCE forward of `plan`: the head's two factors on their own, [B, (H/2)*(W/2)] fp32 -- which = "a": the aux
+        output BEFORE the product with the depth feature (what a forward hook on aux_nets[i] sees), "d": the depth feature alone
+        (the output of depth_nets[i]).  Nothing is kept for a backward."""
+        x = plan.hooked_feature(self.layer)
+        b, h, w, c = x.shape
+        n = (h // 2) * (w // 2)
+        dev = x.device
+        s = ops._stream()
+        if which == "d":
+            if depth is None or depth.dim() < 2:
+                raise ValueError("the depth head needs a (B,1,H,W) depth batch")
+            if self.layer == 9:   # (the kernel the model's own forward runs for this head)
+                return self._depth_feature(depth.float(), b, h, w, n, dev, True)[0]
+            hd, wd = depth.shape[-2:]
+            if (hd >> self.pools, wd >> self.pools) != (h // 2, w // 2):
+                raise ValueError("depth batch of %dx%d does not pool to the %dx%d aux feature of layer %d" % (hd, wd, h // 2, w // 2, self.layer))
+            depth = depth.reshape(b, hd, wd).contiguous().float()
+            feat = torch.empty((b, n), dtype=torch.float32, device=dev)
+            xhat = torch.empty((b, n), dtype=torch.float32, device=dev)
+            lib.rpe_depth_head_fwd_pools(ops._p(depth), ops._p(self.in_w.data), ops._p(self.in_b.data), ops._p(feat), ops._p(xhat), b, hd, wd, self.pools, s)
+            return feat
+        out = torch.empty((b, n), dtype=torch.float32, device=dev)   # no depth feature handed over: out = raw = the un-multiplied value
+        raw = torch.empty((b, n), dtype=torch.float32, device=dev)
+        idx = torch.empty((b, n), dtype=torch.uint8, device=dev)
+        if self.layer == 9:
+            lib.rpe_aux_head_fwd(ops.dtype_code(x), ops._p(x), ops._p(self.conv_w.data), ops._p(self.conv_b.data), None, ops._p(out), out.stride(0),
+                                 ops._p(raw), ops._p(idx), b, h, w, s)
+        else:
+            lib.rpe_aux_head_fwd_c(ops.dtype_code(x), ops._p(x), c, ops._p(self.conv_w.data), ops._p(self.conv_b.data), None, ops._p(out), out.stride(0),
+                                   ops._p(raw), ops._p(idx), b, h, w, s)
+        return out
+
     def _bwd_general(self, d_cols):
         plan, raw, idx, feat, xhat, b, h, w, n = self.saved
         x = plan.hooked_feature(self.layer)

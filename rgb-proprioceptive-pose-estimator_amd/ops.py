@@ -582,3 +582,40 @@ def pose_loss(pred, truth, metric, mode, scale, alpha, eps, want_grad=True):
 
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step):
     lib.rpe_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, step, _stream())
+
+
+def feature_planes(x_nhwc, image=None, out=None, minmax=None):
+    """x [B,H,W,C] (compute dtype, contiguous) -> (planes fp32, minmax fp32): [B,C,H,W] / [B,C,2] for the whole batch, or
+    [C,H,W] / [C,2] for image number `image`.  The widening is exact; minmax is each channel's range over its finite values.
+    out / minmax: contiguous fp32 destinations of those shapes (e.g. one frame's slice of an episode's tensor)."""
+    _chk(x_nhwc, "x")
+    b, h, w, c = x_nhwc.shape
+    dev = x_nhwc.device
+    lead = (b,) if image is None else ()
+    if image is not None and not 0 <= image < b:
+        raise IndexError("feature_planes: image %d of a batch of %d" % (image, b))
+    planes = torch.empty(lead + (c, h, w), dtype=torch.float32, device=dev) if out is None else _chk(out, "out")
+    mm = torch.empty(lead + (c, 2), dtype=torch.float32, device=dev) if minmax is None else _chk(minmax, "minmax")
+    if planes.dtype != torch.float32 or mm.dtype != torch.float32 or tuple(planes.shape) != lead + (c, h, w) or tuple(mm.shape) != lead + (c, 2):
+        raise ValueError("feature_planes: out / minmax must be fp32 of shape %r / %r" % (lead + (c, h, w), lead + (c, 2)))
+    if image is None:
+        lib.rpe_feature_planes_batch(dtype_code(x_nhwc), _p(x_nhwc), b, h, w, c, _p(planes), _p(mm), _stream())
+    else:
+        lib.rpe_feature_planes(dtype_code(x_nhwc), _p(x_nhwc), image, h, w, c, _p(planes), _p(mm), _stream())
+    return planes, mm
+
+
+def mosaic_shape(c, h, w, cols, gutter):
+    rows = (c + cols - 1) // cols
+    return rows * (h + gutter) - gutter, cols * (w + gutter) - gutter
+
+
+def feature_mosaic(planes, minmax, cols, gutter=1, flip_y=True):
+    """planes [C,H,W] fp32 + minmax [C,2] -> uint8 colour-index image of per-channel autoscaled tiles (rpe_feature_mosaic)."""
+    _chk(planes, "planes"), _chk(minmax, "minmax")
+    c, h, w = planes.shape
+    if planes.dtype != torch.float32 or minmax.dtype != torch.float32 or tuple(minmax.shape) != (c, 2):
+        raise ValueError("feature_mosaic: planes [C,H,W] and minmax [C,2] must be fp32")
+    out = torch.empty(mosaic_shape(c, h, w, cols, gutter), dtype=torch.uint8, device=planes.device)
+    lib.rpe_feature_mosaic(_p(planes), _p(minmax), c, h, w, cols, gutter, int(bool(flip_y)), _p(out), _stream())
+    return out

@@ -1,12 +1,29 @@
-"""Model construction helpers.  Mirrors util/model_utils.py:110-147 of the reference
-(`set_parameter_requires_grad`, `import_resnet`); the visualisation helpers of that file are out of
-scope."""
+"""Model construction and inspection helpers.  Mirrors util/model_utils.py of the reference: `set_parameter_requires_grad`,
+`import_resnet` (:110-147) and `visualize_layer` (:10-107), the latter split into `capture_layer` (the layer's output as a
+tensor), `render_layer` (the picture as an array) and `visualize_layer` (show it, or write a PNG).
+
+What a layer string means is the reference's: `tns` with t = f (ResNet: f0 conv1's raw output, f9 bn1 after its in-place ReLU,
+f1..f4 the layer1..layer4 outputs), a (aux_nets[n] BEFORE the product with the depth feature) or d (depth_nets[n]); s = `s` shows
+channel 0, anything else every channel on an n x n grid, n = ceil(sqrt(C)), each tile autoscaled to its own range and drawn with
+row 0 at the bottom.  The values are what the native engine holds after an inference forward (BatchNorm folded into the convs),
+in its compute dtype, widened exactly to fp32 by the capture kernel (csrc/capture.hip).
+
+Deliberate differences from the reference's function: only the trunk and the heads run (the fc / LSTM tail is not needed for
+any layer on offer), so it works for all five model classes and every input the models accept -- also where the reference's
+own forward fails behind the captured layer (`n`, `no` with proprioception, `td`'s unregistered heads); the carried LSTM
+state and the BatchNorm running statistics are untouched; no forward hook is left on the module; every malformed or unavailable
+layer string raises ValueError before any device work (the reference raises AttributeError / IndexError, some of them after its
+forward).  Like the reference it leaves the model in eval().  Do not call it between a training forward and its backward: the
+capture forward reuses the trunk's workspace.
+"""
 import os
 import warnings
 
+import numpy as np
 import torch
 import torch.nn as nn
 
+from .. import ops
 from ..engine import ResNet50Trunk
 
 # An ImageNet checkpoint in torchvision's resnet50 state_dict format, if one is available locally.
@@ -46,3 +63,165 @@ def import_resnet(num_layers, output_dim, feature_extract=True, use_pretrained=T
     set_parameter_requires_grad(model, (feature_extract and use_pretrained))
     model.fc = nn.Linear(model.fc.in_features, output_dim)
     return model, 224
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# layer capture / visualisation (util/model_utils.py:10-107 of the reference)
+# ---------------------------------------------------------------------------------------------------------------------------------
+FEATURE_LAYERS = (0, 9, 1, 2, 3, 4)   # f0 conv1, f9 bn1, f1..f4 layer1..layer4
+
+
+def parse_layer(layer, need_mode=False):
+    """'tns' -> (t, n, single).  t in f / a / d, n a digit, single = (s == 's'); the third character is optional unless
+    `need_mode`.  A bad first letter raises the reference's ValueError (util/model_utils.py:60), every other malformed string a
+    ValueError of its own (the reference: IndexError after its forward)."""
+    if not isinstance(layer, str) or len(layer) < 1:
+        raise ValueError("Layer must be a string of the form 'tns' (e.g. 'f9m'); got: {!r}".format(layer))
+    if layer[0] not in ("f", "d", "a"):
+        raise ValueError("Layer must begin with 'f', 'd', or 'a'! Got: {}".format(layer[0]))
+    if len(layer) < (3 if need_mode else 2):
+        raise ValueError("Layer must be of the form 'tns' (type, number, [s]ingle / [m]ultiple); got: {!r}".format(layer))
+    if layer[1] not in "0123456789":
+        raise ValueError("Layer number must be a digit; got: {!r}".format(layer))
+    return layer[0], int(layer[1]), len(layer) > 2 and layer[2] == "s"
+
+
+def check_layer(model, kind, n):
+    """ValueError unless `model` has layer (kind, n); no device work.  Returns the index into the model's aux heads (a / d)."""
+    if kind == "f":
+        if n not in FEATURE_LAYERS:
+            raise ValueError("ResNet layers f0 (conv1), f9 (bn1) and f1..f4 (layer1..layer4) exist; got: f{}".format(n))
+        return None
+    hooks = getattr(model, "_hooks", None)
+    if getattr(model, "aux_nets", None) is None or not hooks:
+        raise ValueError("{} has no aux / depth heads (layer {}{})".format(type(model).__name__, kind, n))
+    if n >= len(hooks):
+        raise ValueError("{}{}: the model has {} aux / depth head(s)".format(kind, n, len(hooks)))
+    if kind == "d" and not model.use_depth:
+        raise ValueError("d{}: the model was built with use_depth=False, its depth heads never run".format(n))
+    return n
+
+
+def _as_image_batch(img):
+    """-> (lead shape, frames?) of an image argument: float (..., 3, H, W) or raw uint8 frames (..., Hs, Ws, 3), up to two leading
+    dimensions (sequence-shaped input is flattened as the models do)."""
+    if not isinstance(img, torch.Tensor) or img.dim() < 3 or img.dim() > 5:
+        raise ValueError("img must be a (3,H,W), (B,3,H,W) or (S,N,3,H,W) tensor (uint8 frames: channels last)")
+    frames = img.dtype == torch.uint8
+    if (img.shape[-1] if frames else img.shape[-3]) != 3:
+        raise ValueError("img must have 3 channels; got shape {}".format(tuple(img.shape)))
+    return tuple(img.shape[:-3]), frames
+
+
+def _capture(model, layer, img, depth, need_mode):
+    """-> (planes [B,C,H,W] fp32, minmax [B,C,2] fp32, lead shape, single)"""
+    kind, n, single = parse_layer(layer, need_mode)
+    head = check_layer(model, kind, n)
+    lead, frames = _as_image_batch(img)
+    trunk = model.trunk
+    hw = tuple(trunk.crop_hw) if frames else tuple(img.shape[-2:])
+    if head is not None:
+        hooked = model._hooks[head]
+        if hooked != 9 and hw != (224, 224):
+            raise ValueError("hooks other than bn1 are sized for 224x224 inputs (as the reference's dummy forward is)")
+        if kind == "d" and depth is None:
+            raise ValueError("d{}: the depth head needs the depth image".format(n))
+    model.eval()
+    model._materialize(img.device)   # (raises for CPU tensors: there is no CPU path)
+    x = img.reshape(-1, *img.shape[-3:]).contiguous()
+    if not frames:
+        x = x.float()
+    b = x.shape[0]
+    if depth is not None and kind == "d":
+        depth = depth.reshape(b, 1, *depth.shape[-2:])
+    rows = torch.empty((1, ops.pad4(model.latent_dim)), dtype=torch.float32, device=x.device)
+    # Every image goes through the trunk on its own, on the batch-1 plan a rollout frame uses: the engine picks its reduction
+    # order by the number of output rows (few rows: the long reductions of the deep layers are split), so a frame's values would
+    # otherwise depend on how many other frames ride along; and a capture of an odd batch size then neither allocates a plan of
+    # its own nor evicts the training plan (ResNet50Trunk.max_plans).  Each frame's planes kernel writes its slice of the result.
+    # f0 is conv1's RAW output, which the folded inference stem does not write: without a conv1 hook of its own the model keeps it
+    # for these forwards only.  The switch changes the packed inference copy of conv1's weight, which captured rollout frames
+    # replay as it stands, so one more forward with the switch back restores it (same bytes: the packing is deterministic).
+    raw_stem = kind == "f" and n == 0 and not trunk.keep_stem_raw
+    planes = minmax = None
+    with torch.no_grad():
+        if raw_stem:
+            trunk.keep_stem_raw = True
+        try:
+            for i in range(b):
+                plan = trunk.run(x[i:i + 1], rows, False)
+                if kind == "f":
+                    v = plan.hooked_feature(n)
+                else:
+                    _, h, w, _ = plan.hooked_feature(model._hooks[head]).shape
+                    v = model._aux_ops[head].parts(plan, None if depth is None else depth[i:i + 1], kind).view(1, h // 2, w // 2, 1)
+                if planes is None:
+                    _, h, w, c = v.shape
+                    planes = torch.empty((b, c, h, w), dtype=torch.float32, device=x.device)
+                    minmax = torch.empty((b, c, 2), dtype=torch.float32, device=x.device)
+                ops.feature_planes(v, image=0, out=planes[i], minmax=minmax[i])
+        finally:
+            if raw_stem:
+                trunk.keep_stem_raw = False
+                trunk.run(x[:1], rows, False)
+    return planes, minmax, lead, single
+
+
+def capture_layer(model, layer, img, depth=None):
+    """What layer `layer` ('tn', see the module docstring; a third character is ignored) holds for `img`, as an fp32 tensor on the
+    model's device: img (3,H,W) -> (C',H',W'); (B,3,H,W) -> (B,C',H',W'); (S,N,3,H,W) -> (S*N,C',H',W').  a / d layers have
+    C' = 1.  uint8 frames (..., Hs, Ws, 3) go through the trunk's own resize / crop / normalise staging."""
+    planes, _, lead, _ = _capture(model, layer, img, depth, need_mode=False)
+    return planes[0] if not lead else planes
+
+
+def layer_index_image(model, layer, img, depth=None, *, gutter=1, flip_y=True):
+    """The picture of `render_layer` before the colour lookup: (uint8 index image as a numpy array, (C, H, W, cols) of the grid).
+    One image only ((3,H,W), or leading dimensions of size 1)."""
+    planes, minmax, lead, single = _capture(model, layer, img, depth, need_mode=True)
+    if planes.shape[0] != 1:
+        raise ValueError("one image at a time can be drawn; got a batch of {}".format(planes.shape[0]))
+    planes, minmax = planes[0], minmax[0]
+    if single:
+        planes, minmax = planes[:1], minmax[:1]
+    c, h, w = planes.shape
+    cols = int(np.ceil(np.sqrt(c)))
+    idx = ops.feature_mosaic(planes, minmax, cols, gutter=gutter, flip_y=flip_y)
+    return idx.cpu().numpy(), (c, h, w, cols)
+
+
+def colour_table():
+    """256 x 3 uint8: matplotlib's default colormap (viridis) when matplotlib is importable, a grey ramp otherwise."""
+    try:
+        import matplotlib
+        return np.ascontiguousarray(matplotlib.colormaps["viridis"](np.arange(256), bytes=True)[:, :3])
+    except Exception:
+        return np.repeat(np.arange(256, dtype=np.uint8)[:, None], 3, axis=1)
+
+
+def render_layer(model, layer, img, depth=None, *, gutter=1, flip_y=True):
+    """The reference's figure for `layer` ('tns') as a uint8 (rows, cols, 3) array: every tile autoscaled to its own range on the
+    device (rpe_feature_mosaic), coloured on the host; gutters and unused grid cells are white."""
+    idx, (c, h, w, cols) = layer_index_image(model, layer, img, depth, gutter=gutter, flip_y=flip_y)
+    rgb = colour_table()[idx]
+    oy, ox = np.arange(idx.shape[0]), np.arange(idx.shape[1])
+    blank = (oy % (h + gutter) >= h)[:, None] | (ox % (w + gutter) >= w)[None, :]
+    blank |= ((oy // (h + gutter))[:, None] * cols + (ox // (w + gutter))[None, :]) >= c
+    rgb[blank] = 255
+    return rgb
+
+
+def visualize_layer(model, layer, img, depth=None, *, out=None):
+    """Visualizes the output of a layer of `model` (util/model_utils.py:10-107).  Without `out` the picture is shown with
+    matplotlib; with `out` it is written there as a PNG and no window is opened."""
+    rgb = render_layer(model, layer, img, depth)
+    if out is not None:
+        from PIL import Image
+        Image.fromarray(rgb).save(out, format="PNG")
+        return out
+    import matplotlib.pyplot as plt
+    plt.figure()
+    plt.imshow(rgb)
+    plt.setp(plt.gcf().get_axes(), xticks=[], yticks=[])
+    plt.show()
+    return None
