@@ -239,6 +239,15 @@ int rpe_stage_frames_u8_resized(int dtype, const unsigned char* frames, void* ou
                                 const int* xb, const int* xk, int ksx, const int* yb, const int* yk, int ksy, unsigned char* tmp, const float* mean3_host,
                                 const float* std3_host, void* stream);
 
+/* replaces: the CPU depth transform ToPILImage -> Resize(256) -> CenterCrop(224) -> ToTensor (util/data_utils.py:55-60) for raw
+ * fp32 depth frames [B][Hs][Ws]: Pillow's 32-bit-float bilinear resample (mode F: double accumulation over ascending taps, the
+ * horizontal pass rounded to fp32 before the vertical one) to Hr x Wr, of which out [B][H][W] fp32 receives the window
+ * [top, top + H) x [left, left + W) -- bit for bit what Pillow writes; ToTensor does not rescale a float image.  xb/yb as in
+ * rpe_stage_frames_u8_resized; xk/yk: [Wr][ksx] / [Hr][ksy] DOUBLE weights (device pointers; a pass whose size does not change
+ * takes nulls, with both null this is a crop copy).  One launch, no scratch. */
+int rpe_stage_depth_f32_resized(const float* frames, float* out, int B, int Hs, int Ws, int Hr, int Wr, int top, int left, int H, int W,
+                                const int* xb, const double* xk, int ksx, const int* yb, const double* yk, int ksy, void* stream);
+
 /* ------------------------------------------------------------------ batch norm */
 /* replaces: nn.BatchNorm2d (train mode: biased batch variance, eps, momentum with
  * unbiased running variance) + the in-place nn.ReLU and `out += identity` of the

@@ -83,6 +83,7 @@ _SPEC = {
     "rpe_stage_image_nhwc4": (I, [I, P, P, I, I, I, P]),
     "rpe_stage_frames_u8": (I, [I, P, P, I, I, I, I, I, POINTER(c_float), POINTER(c_float), P]),
     "rpe_stage_frames_u8_resized": (I, [I, P, P, I, I, I, I, I, I, I, I, I, P, P, I, P, P, I, P, POINTER(c_float), POINTER(c_float), P]),
+    "rpe_stage_depth_f32_resized": (I, [P, P, I, I, I, I, I, I, I, I, I, P, P, I, P, P, I, P]),
     "rpe_bn_finalize": (I, [P, I, I, L, P, P, P, P, P, F, F, P, P, P, P, P, P]),
     "rpe_bn_eval_affine": (I, [I, P, P, P, P, F, P, P, P]),
     "rpe_bn_apply": (I, [I, P, P, P, P, P, L, I, I, P]),

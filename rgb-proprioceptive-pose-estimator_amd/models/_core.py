@@ -66,6 +66,24 @@ def _make_depth(h, w):
     return _DepthStack(*([nn.AvgPool2d(2) for _ in range(n_pool)] + [nn.InstanceNorm2d(1, affine=True), nn.Flatten()]))
 
 
+def is_raw_depth(img, depth):
+    """A depth batch is RAW -- robosuite's channels-last fp32 (..., Hs, Ws, 1) -- iff it comes beside raw uint8 frames (..., Hs, Ws, 3)
+    of the same geometry.  A preprocessed (..., 1, H, W) tensor can never have that shape."""
+    return img.dtype == torch.uint8 and tuple(depth.shape) == tuple(img.shape[:-1]) + (1,)
+
+
+def stage_raw_depth(img, depth, trunk):
+    """Raw depth -> the (B, 1, H, W) fp32 plane at the trunk's crop size (ops.stage_depth: the reference's depth_transform on the
+    device); anything else is returned as it came, for the existing preprocessed path.  A channels-last depth that does NOT sit beside
+    uint8 frames of its own geometry is an error, not a guess."""
+    if is_raw_depth(img, depth):
+        return ops.stage_depth(depth.contiguous().float(), tuple(trunk.crop_hw), trunk.resize_to)
+    if depth.dim() >= 3 and depth.shape[-1] == 1 and depth.shape[-3] != 1:
+        raise ValueError("raw depth (..., Hs, Ws, 1) goes with raw uint8 frames (..., Hs, Ws, 3) of the same Hs x Ws; got depth %r beside %s "
+                         "img %r" % (tuple(depth.shape), str(img.dtype).split(".")[-1], tuple(img.shape)))
+    return depth
+
+
 class _ModelFn(torch.autograd.Function):
     """One autograd node for a whole model call.  `anchor` is a trainable parameter: it only makes the
     node part of the graph -- gradients are written into the arena by the kernels, not returned."""
@@ -231,6 +249,8 @@ class PoseModelBase(nn.Module):
         """img (B,3,H,W); rows [B, ld] fp32: columns [0,L) <- ResNet latent, [L, L+aux) <- aux head."""
         # the bn1 head of a training forward rides on the engine's stem pass (headops.AuxHeadOp.bind_fused): it is bound before the run
         cols, fused, off = {}, set(), self.latent_dim
+        if self.use_depth and depth is not None:
+            depth = stage_raw_depth(img, depth, self.trunk)
         if self.aux_nets is not None:
             for op in self._aux_ops:
                 c, h, w = self.HOOK_SHAPES[op.layer]

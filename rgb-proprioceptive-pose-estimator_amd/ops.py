@@ -619,3 +619,56 @@ def feature_mosaic(planes, minmax, cols, gutter=1, flip_y=True):
     out = torch.empty(mosaic_shape(c, h, w, cols, gutter), dtype=torch.uint8, device=planes.device)
     lib.rpe_feature_mosaic(_p(planes), _p(minmax), c, h, w, cols, gutter, int(bool(flip_y)), _p(out), _stream())
     return out
+
+
+_DEPTH_TABLES = {}
+
+
+def _depth_tables(hs, ws, hr, wr, device):
+    """device tap tables of the Pillow-exact fp32 resize for one frame geometry (built once, kept: a captured graph replays the
+    staging without a host-to-device copy)"""
+    from .util.data_utils import pil_bilinear_tables_f64
+    key = (hs, ws, hr, wr, device.type, device.index)
+    tabs = _DEPTH_TABLES.get(key)
+    if tabs is None:
+        tabs = []
+        for i, o in ((ws, wr), (hs, hr)):
+            if i == o:
+                tabs.append((None, None, 0))
+            else:
+                bounds, kk = pil_bilinear_tables_f64(i, o)
+                tabs.append((torch.from_numpy(bounds).to(device), torch.from_numpy(kk).to(device), kk.shape[1]))
+        _DEPTH_TABLES[key] = tabs
+    return tabs
+
+
+def stage_depth_window(raw, hr, wr, top, left, h, w):
+    """raw [B, Hs, Ws] fp32 -> [B, 1, h, w] fp32: the window [top, top + h) x [left, left + w) of Pillow's mode-F bilinear resize of
+    every frame to hr x wr (rpe_stage_depth_f32_resized), bit for bit."""
+    _chk(raw, "raw")
+    if raw.dim() != 3 or raw.dtype != torch.float32:
+        raise ValueError("stage_depth_window: raw must be [B, Hs, Ws] fp32; got %s %r" % (raw.dtype, tuple(raw.shape)))
+    b, hs, ws = raw.shape
+    if top < 0 or left < 0 or top + h > hr or left + w > wr:
+        raise ValueError("stage_depth_window: the %dx%d window at (%d, %d) leaves the %dx%d resized frame" % (h, w, top, left, hr, wr))
+    (xb, xk, ksx), (yb, yk, ksy) = _depth_tables(hs, ws, hr, wr, raw.device)
+    out = torch.empty((b, 1, h, w), dtype=torch.float32, device=raw.device)
+    lib.rpe_stage_depth_f32_resized(_p(raw), _p(out), b, hs, ws, hr, wr, top, left, h, w, _p(xb), _p(xk), ksx, _p(yb), _p(yk), ksy, _stream())
+    return out
+
+
+def stage_depth(raw, crop_hw=(224, 224), size=256):
+    """The reference's depth_transform (ToPILImage -> Resize(size) -> CenterCrop(crop_hw) -> ToTensor, util/data_utils.py:55-60) on the
+    device: raw fp32 depth frames [B, Hs, Ws] or channels-last (..., Hs, Ws, 1) -> [B, 1, H, W] fp32, bit for bit what Pillow gives."""
+    from .util.data_utils import crop_origin, resized_hw
+    if raw.dim() >= 4 and raw.shape[-1] == 1:
+        raw = raw.reshape(-1, raw.shape[-3], raw.shape[-2])
+    if raw.dim() != 3 or raw.dtype != torch.float32:
+        raise ValueError("stage_depth: raw depth is fp32 [B, Hs, Ws] or (..., Hs, Ws, 1); got %s %r" % (raw.dtype, tuple(raw.shape)))
+    hs, ws = raw.shape[-2:]
+    h, w = crop_hw
+    hr, wr = resized_hw(hs, ws, size)
+    if min(hr, wr) < min(h, w) or hr < h or wr < w:
+        raise ValueError("frames of %dx%d resize to %dx%d, smaller than the %dx%d crop" % (hs, ws, hr, wr, h, w))
+    top, left = crop_origin(hr, wr, h, w)
+    return stage_depth_window(raw.contiguous(), hr, wr, top, left, h, w)

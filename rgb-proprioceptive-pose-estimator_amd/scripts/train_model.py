@@ -13,6 +13,7 @@ episodes are sharded over ranks and gradients SUM-all-reduced over RCCL.
 import argparse
 import os
 import sys
+import warnings
 
 import torch
 
@@ -59,6 +60,9 @@ def build_parser():
     p.add_argument("--optimizer", choices=["fused", "torch"], default="fused", help="FusedAdam (one HIP kernel) or torch.optim.Adam")
     p.add_argument("--episodes_seed", type=int, default=1234, help="seed of the synthetic episode generator")
     p.add_argument("--no_save", action="store_true", help="do not write the best-validation checkpoint")
+    p.add_argument("--episodes", type=str, default=None, metavar="FILE.npz",
+                   help="recorded raw episodes (util.data_utils.RecordedEpisodeDataset: imgs uint8 (E,T,Hs,Ws,3), depths float32 (E,T,Hs,Ws,1), "
+                        "true_self / true_other / true_obj (E,T,7)) instead of synthetic ones; the horizon is the file's")
     return p
 
 
@@ -95,7 +99,7 @@ def main(argv=None):
     from rgb_proprioceptive_pose_estimator_amd.dist import init_from_env
     from rgb_proprioceptive_pose_estimator_amd.models import PoseDistanceLoss
     from rgb_proprioceptive_pose_estimator_amd.optim import FusedAdam
-    from rgb_proprioceptive_pose_estimator_amd.util.data_utils import SyntheticEpisodeDataset
+    from rgb_proprioceptive_pose_estimator_amd.util.data_utils import RecordedEpisodeDataset, SyntheticEpisodeDataset
     from rgb_proprioceptive_pose_estimator_amd.util.learn_utils import train
 
     rank, world, local = init_from_env()
@@ -120,8 +124,14 @@ def main(argv=None):
         raise SystemExit("--dtype f16 needs --optimizer fused: the loss-scale unscale / skip logic lives in FusedAdam.step (amp.py)")
     opt_cls = FusedAdam if args.optimizer == "fused" else torch.optim.Adam
     optimizer = opt_cls(model.parameters(), lr=args.lr)
-    dataset = SyntheticEpisodeDataset(horizon=args.horizon, use_depth=args.use_depth, obj_name=args.obj_name, is_two_arm="TwoArm" in args.env,
-                                      motion=args.motion, seed=args.episodes_seed + 1000 * rank, device=device, env_name=args.env)
+    if args.episodes:
+        dataset = RecordedEpisodeDataset(args.episodes, use_depth=args.use_depth, obj_name=args.obj_name, seed=args.episodes_seed + 1000 * rank)
+        if args.horizon != build_parser().get_default("horizon") and args.horizon != dataset.env.horizon and rank == 0:
+            warnings.warn("--horizon {} ignored: the episodes of {} have {} steps".format(args.horizon, args.episodes, dataset.env.horizon))
+        args.horizon = dataset.env.horizon
+    else:
+        dataset = SyntheticEpisodeDataset(horizon=args.horizon, use_depth=args.use_depth, obj_name=args.obj_name, is_two_arm="TwoArm" in args.env,
+                                          motion=args.motion, seed=args.episodes_seed + 1000 * rank, device=device, env_name=args.env)
     params = {"camera_name": args.camera_name, "noise_scale": args.noise_scale}
     if rank == 0:
         print("Training...")

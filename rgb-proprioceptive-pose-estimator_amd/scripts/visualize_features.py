@@ -26,7 +26,8 @@ def build_vis_parser():
     p = build_parser()
     p.add_argument("--model_path", type=str, default=None, help="state_dict .pth to load (reference key names)")
     p.add_argument("--frames", type=str, default=None, help=".npy of uint8 camera frames (T, Hs, Ws, 3); default: a seeded synthetic episode")
-    p.add_argument("--depth", type=str, default=None, help=".npy of depth images (T, H, W) or (T, 1, H, W) at the network's input size (--use_depth)")
+    p.add_argument("--depth", type=str, default=None, help=".npy of depth images for --use_depth: (T, H, W) or (T, 1, H, W) at the network's input size, or RAW float32 "
+                   "(T, Hs, Ws) or (T, Hs, Ws, 1) with the geometry of --frames (resized and cropped on the device, as Pillow would)")
     p.add_argument("--frame", type=int, default=0, help="which frame of the episode to show")
     p.add_argument("--layer", action="append", default=None, help="layer string 'tns' (f9m, a0s, ..); repeatable; default: prompt")
     p.add_argument("--out", type=str, default=None, help="directory for <layer>.png; default: show with matplotlib")
@@ -76,8 +77,15 @@ def main(argv=None):
         img = torch.from_numpy(np.ascontiguousarray(raw_img)).cuda()
         if args.depth:
             d = np.load(args.depth)[args.frame]
-            raw_depth = d.reshape(d.shape[-2:])
-            depth = torch.from_numpy(np.ascontiguousarray(raw_depth, dtype=np.float32)).cuda().view(1, 1, *raw_depth.shape)
+            raw_depth = d[..., 0] if d.ndim == 3 and d.shape[-1] == 1 and d.shape[0] != 1 else d.reshape(d.shape[-2:])
+            depth = torch.from_numpy(np.ascontiguousarray(raw_depth, dtype=np.float32)).cuda()
+            if raw_depth.shape == tuple(model.trunk.crop_hw):
+                depth = depth.view(1, 1, *raw_depth.shape)     # already at the network's input size
+            elif raw_depth.shape == raw_img.shape[:2]:
+                depth = depth.view(*raw_depth.shape, 1)        # raw, the frames' geometry: resized and cropped on the device like them
+            else:
+                raise SystemExit("--depth: frames of {}x{} are neither the network's input size nor the {}x{} of --frames".format(
+                    *raw_depth.shape, *raw_img.shape[:2]))
     else:
         ep = synthetic_batch((args.horizon, 1), 3, with_depth=args.use_depth, noise_scale=args.noise_scale)
         img = ep["img"][args.frame, 0]

@@ -7,7 +7,8 @@ episodes at timestep t, util/data_utils.py:62-73), the 6-tuple, `refresh_data`, 
 `standardize_quat`.  SyntheticEpisodeDataset fills the same tensors with seeded Robosuite-shaped data
 (ImageNet-normalised uint8 noise images, workspace-bounded positions, unit quaternions with w >= 0,
 proprioception = truth + N(0, noise_scale I) with the quaternion renormalised, util/data_utils.py:162-176),
-generated directly in HBM.
+generated directly in HBM.  RecordedEpisodeDataset reads episodes recorded from the simulator elsewhere back from a file, raw, and
+leaves every image transform to the device.
 """
 import types
 
@@ -47,6 +48,35 @@ def pil_bilinear_tables(in_size, out_size):
     kk = np.floor(0.5 + w * (1 << PIL_PRECISION_BITS)).astype(np.int32)   # weights are >= 0 for the triangle filter: (int)(0.5 + v)
     kk = np.where(taps < xmax[:, None], kk, 0).astype(np.int32)
     return np.stack([xmin, xmax], 1).astype(np.int32), kk
+
+
+def pil_bilinear_tables_f64(in_size, out_size):
+    """Tap tables of Pillow's 32-bit-float bilinear resample along one axis (what `Resize(256)` runs on the mode-F image that
+    ToPILImage makes of a float32 depth frame, util/data_utils.py:55-60 of the reference): (bounds [out, 2] int32 as in
+    `pil_bilinear_tables`, weights [out, ksize] float64).  Resample.c precompute_coeffs, operation for operation: the filter argument
+    is MULTIPLIED by 1 / filterscale, and the weights are summed in ascending tap order before the division -- the device kernel
+    (csrc/depth_stage.hip) reproduces Pillow's pixels bit for bit only from bit-identical weights."""
+    import math
+    import numpy as np
+    scale = filterscale = in_size / out_size
+    if filterscale < 1.0:
+        filterscale = 1.0
+    support = filterscale
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    xx = np.arange(out_size, dtype=np.float64)
+    center = (xx + 0.5) * scale
+    xmin = np.where(center - support + 0.5 < 0, 0, (center - support + 0.5).astype(np.int64))
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), in_size) - xmin
+    taps = np.arange(ksize, dtype=np.float64)[None, :]
+    t = np.abs((taps + xmin[:, None] - center[:, None] + 0.5) * ss)
+    w = np.where((t < 1.0) & (taps < xmax[:, None]), 1.0 - t, 0.0)
+    ww = np.zeros(out_size, dtype=np.float64)
+    for k in range(ksize):   # (np.sum pairs its additions up; Pillow adds tap by tap)
+        ww = ww + w[:, k]
+    ww = ww[:, None]
+    w = np.where(ww != 0.0, w / np.where(ww != 0.0, ww, 1.0), w)
+    return np.stack([xmin, xmax], 1).astype(np.int32), np.ascontiguousarray(w)
 
 
 def resized_hw(h, w, size=256):
@@ -140,6 +170,106 @@ class SyntheticEpisodeDataset(Dataset):
         x1 = tm(d["true_other"]) if self.is_two_arm else None
         obj = tm(d["true_obj"]) if self.obj_name is not None else None
         return img, depth, tm(d["measurement_self"]), tm(d["true_self"]), x1, obj
+
+
+class RecordedEpisodeDataset(Dataset):
+    """MultiEpisodeDataset-shaped source of episodes RECORDED from the simulator elsewhere and read back from one `.npz` file: the
+    keys of the reference's `MultiEpisodeDataset.data` (util/data_utils.py:85-92), raw instead of transformed --
+
+        imgs       (E, T, Hs, Ws, 3) uint8      camera frames as robosuite returns them
+        depths     (E, T, Hs, Ws, 1) float32    optional; needed for use_depth
+        true_self  (E, T, 7) float32            end-effector pose (x, y, z, qx, qy, qz, qw)
+        true_other (E, T, 7) float32            optional; needed for a two-arm environment
+        true_obj   (E, T, 7) float32            optional; needed for obj_name
+        env_name   string                       optional, default "Recorded"; "TwoArm" in it means two arms, as in the reference
+
+    The data stays on the HOST: `__getitem__(t)` hands out the reference's 6-tuple of host tensors with frames and depth raw, and
+    train() moves them through FramePrefetcher; resize, crop and normalisation run on the device (rpe_stage_frames_u8[_resized],
+    rpe_stage_depth_f32_resized).  `refresh_data` walks through the file: each call selects the next `num_episodes` episodes in
+    file order, wrapping around, and draws fresh measurement noise (util/data_utils.py:162-167)."""
+
+    _POSES = ("true_self", "true_other", "true_obj")
+
+    def __init__(self, path, use_depth=False, obj_name=None, seed=1234):
+        import numpy as np
+        with np.load(path, allow_pickle=False) as f:
+            arrays = {k: f[k] for k in f.files}
+        env_name = str(arrays.pop("env_name")) if "env_name" in arrays else "Recorded"
+        self._check(arrays)
+        self.is_two_arm = "TwoArm" in env_name
+        if use_depth and "depths" not in arrays:
+            raise ValueError("{}: use_depth needs the 'depths' array".format(path))
+        if obj_name is not None and "true_obj" not in arrays:
+            raise ValueError("{}: obj_name={!r} needs the 'true_obj' array".format(path, obj_name))
+        if self.is_two_arm and "true_other" not in arrays:
+            raise ValueError("{}: a two-arm environment ({}) needs the 'true_other' array".format(path, env_name))
+        self.path, self.use_depth, self.obj_name, self.seed = path, use_depth, obj_name, seed
+        self.episodes = {k: torch.from_numpy(v) for k, v in arrays.items() if k != "depths" or use_depth}
+        self.num_recorded = arrays["imgs"].shape[0]
+        self.data = None
+        self._next = 0
+        self._gen = torch.Generator().manual_seed(int(seed))
+        # train() only reads type(env).__name__ and env.horizon (util/learn_utils.py:84-89)
+        self.env = type(env_name, (), {})()
+        self.env.horizon = arrays["imgs"].shape[1]
+
+    @classmethod
+    def _check(cls, arrays):
+        """ValueError unless the arrays have the file format's ranks, dtypes and matching leading dimensions"""
+        import numpy as np
+        unknown = set(arrays) - {"imgs", "depths"} - set(cls._POSES)
+        if unknown:
+            raise ValueError("unknown arrays {}: the file holds imgs, depths, true_self, true_other, true_obj, env_name".format(sorted(unknown)))
+        for need in ("imgs", "true_self"):
+            if need not in arrays:
+                raise ValueError("the '{}' array is required".format(need))
+        imgs = arrays["imgs"]
+        if imgs.dtype != np.uint8 or imgs.ndim != 5 or imgs.shape[-1] != 3 or 0 in imgs.shape:
+            raise ValueError("imgs must be uint8 (E, T, Hs, Ws, 3); got {} {}".format(imgs.dtype, imgs.shape))
+        if "depths" in arrays:
+            d = arrays["depths"]
+            if d.dtype != np.float32 or d.shape != imgs.shape[:-1] + (1,):
+                raise ValueError("depths must be float32 {}; got {} {}".format(imgs.shape[:-1] + (1,), d.dtype, d.shape))
+        for k in cls._POSES:
+            if k in arrays and (arrays[k].dtype != np.float32 or arrays[k].shape != imgs.shape[:2] + (7,)):
+                raise ValueError("{} must be float32 {}; got {} {}".format(k, imgs.shape[:2] + (7,), arrays[k].dtype, arrays[k].shape))
+
+    @classmethod
+    def save(cls, path, env_name="Recorded", **arrays):
+        """Write an episode file: imgs=, true_self= and optionally depths=, true_other=, true_obj= (numpy arrays or tensors), checked
+        against the format above."""
+        import numpy as np
+        arrays = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in arrays.items() if v is not None}
+        cls._check(arrays)
+        with open(path, "wb") as f:   # (np.savez would append ".npz" to a bare name)
+            np.savez(f, env_name=np.array(str(env_name)), **arrays)
+        return path
+
+    def __len__(self):
+        return self.data["measurement_self"].size(1)
+
+    def __getitem__(self, index):
+        d = self.data
+        img = d["imgs"][:, index]
+        depth = d["depths"][:, index] if self.use_depth else torch.empty(0)
+        x0bar = d["measurement_self"][:, index]
+        x0 = d["true_self"][:, index]
+        x1 = d["true_other"][:, index] if self.is_two_arm else torch.empty_like(x0)
+        obj = d["true_obj"][:, index] if self.obj_name is not None else torch.empty_like(x0)
+        return img, depth, x0bar, x0, x1, obj
+
+    def refresh_data(self, num_episodes, camera_name=None, noise_scale=0.001):
+        if num_episodes > self.num_recorded:
+            raise ValueError("{} holds {} episodes; {} were asked for".format(self.path, self.num_recorded, num_episodes))
+        sel = (torch.arange(num_episodes) + self._next) % self.num_recorded
+        self._next = int(self._next + num_episodes) % self.num_recorded
+        self.selected = sel.tolist()
+        data = {k: v[sel] for k, v in self.episodes.items()}
+        x0 = data["true_self"]
+        # measurement = truth + N(0, noise_scale I), the quaternion part renormalised (util/data_utils.py:162-167)
+        x0bar = x0 + (noise_scale ** 0.5) * torch.randn(x0.shape, generator=self._gen)
+        data["measurement_self"] = torch.cat([x0bar[..., :3], x0bar[..., 3:] / x0bar[..., 3:].norm(dim=-1, keepdim=True)], dim=-1)
+        self.data = data
 
 
 class FramePrefetcher:

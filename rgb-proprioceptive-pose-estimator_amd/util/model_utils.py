@@ -133,6 +133,9 @@ def _capture(model, layer, img, depth, need_mode):
         x = x.float()
     b = x.shape[0]
     if depth is not None and kind == "d":
+        if frames and depth.dim() >= 3 and tuple(depth.shape[-3:]) == tuple(x.shape[1:3]) + (1,):
+            # raw channels-last depth beside raw frames (the models' shape rule, models/_core.py): the depth transform on the device
+            depth = ops.stage_depth(depth.reshape(b, *x.shape[1:3]).float(), tuple(trunk.crop_hw), trunk.resize_to)
         depth = depth.reshape(b, 1, *depth.shape[-2:])
     rows = torch.empty((1, ops.pad4(model.latent_dim)), dtype=torch.float32, device=x.device)
     # Every image goes through the trunk on its own, on the batch-1 plan a rollout frame uses: the engine picks its reduction
