@@ -409,6 +409,30 @@ int rpe_lstm_cell_bwd(const float* gates_act, const float* c_prev, const float* 
 int rpe_pose_loss(const float* pred, const float* truth, long n, int metric, int mode, float scale, float alpha, float eps, float* out3,
                   float* grad, void* stream);
 
+/* replaces: the per-sample numpy loop of PoseDistanceLoss's "val" branch (models/losses.py:95-113) as rollout() calls it once per
+ * step, and the quaternion normalisation of the printed pose (util/learn_utils.py:451-452,488-489).
+ * pred, truth [n][7] fp32.  pos_err[i] = sqrtf(|dp_i|^2 + eps); ori_err[i] = |angle_i| in radians; pose_unit[n][7] (nullable) =
+ * the predicted position copied and the predicted quaternion divided by its norm.  The arithmetic is that of the two validation
+ * sums of rpe_pose_loss (one device function serves both): fp32 w = <qhat, t> / |t|^2 clipped to [-1, 1]; in double, angle 0
+ * where sqrt(1 - w^2) == 0, else 2 acos(w), minus 2 pi above pi, then |.|.
+ * An all-zero predicted quaternion gives NaN in ori_err[i] and in the quaternion of pose_unit[i], as in the reference; pos_err[i]
+ * stays finite and no other row is touched.  (The SUM in rpe_pose_loss's out3[2] counts such a row as 0: its fp32 clip drops
+ * the NaN.)  One sample per thread, grid-stride, any n >= 1. */
+int rpe_pose_errors(const float* pred, const float* truth, long n, float eps, float* pos_err, float* ori_err, float* pose_unit,
+                    void* stream);
+
+/* replaces: np.sum / np.average per episode and np.average / np.std over all steps of the evaluation print-out
+ * (util/learn_utils.py:527-538), on the device.
+ * err [E][T] fp32 (episode-major).  out: 3 + 2 E doubles --
+ *     out[0]            mean over all E*T values
+ *     out[1]            population standard deviation (numpy's ddof = 0), two passes: the mean, then the squared deviations
+ *     out[2]            maximum
+ *     out[3 .. 3+E)     sum of each episode's T values
+ *     out[3+E .. 3+2E)  mean of each episode's T values
+ * fp64 accumulation in one fixed order by a single workgroup, no atomics: two calls give the same bits.  A NaN in `err`
+ * propagates into every figure it takes part in (mean, std, max, its episode's sum and mean). */
+int rpe_error_stats(const float* err, int E, int T, double* out, void* stream);
+
 /* replaces: torch.optim.Adam(model.parameters(), lr).step() (scripts/train_model.py:228,
  * util/learn_utils.py:179) over one flat parameter / gradient / moment buffer. */
 int rpe_adam_step(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2, double eps, int step,

@@ -126,6 +126,8 @@ _SPEC = {
     "rpe_lstm_cell_fwd": (I, [P, P, P, P, P, P, I, I, P]),
     "rpe_lstm_cell_bwd": (I, [P, P, P, P, P, P, I, I, P]),
     "rpe_pose_loss": (I, [P, P, L, I, I, F, F, F, P, P, P]),
+    "rpe_pose_errors": (I, [P, P, L, F, P, P, P, P]),
+    "rpe_error_stats": (I, [P, I, I, P, P]),
     "rpe_adam_step": (I, [P, P, P, P, L, D, D, D, D, I, P]),
     "rpe_amp_unscale": (I, [P, L, P, P]),
     "rpe_amp_update": (I, [P, F, F, I, P]),

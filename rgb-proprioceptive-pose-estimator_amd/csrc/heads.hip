@@ -410,6 +410,40 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float* __restr
 }
 
 // ---------------------------------------------------------------------------------------------
+// The validation half of PoseDistanceLoss for ONE sample (models/losses.py:95-113), shared by pose_loss_kernel (which sums it) and
+// pose_errors_kernel (which stores it per sample): both run these very operations, in this order.
+// ---------------------------------------------------------------------------------------------
+// squared position difference, summed x, y, z in that order; d[k] = p[k] - t[k]
+__device__ __forceinline__ float pose_pos_sq(const float* __restrict__ p, const float* __restrict__ t, float d[3]) {
+    float sq = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { d[k] = p[k] - t[k]; sq += d[k] * d[k]; }
+    return sq;
+}
+
+// qhat = q / |q| (no eps: an all-zero quaternion yields NaN, as in the reference); returns <qhat, t>
+__device__ __forceinline__ float pose_unit_quat(const float* __restrict__ p, const float* __restrict__ t, float h[4], float& mag) {
+    const float q0 = p[3], q1 = p[4], q2 = p[5], q3 = p[6];
+    mag = sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
+    h[0] = q0 / mag; h[1] = q1 / mag; h[2] = q2 / mag; h[3] = q3 / mag;
+    return h[0] * t[3] + h[1] * t[4] + h[2] * t[5] + h[3] * t[6];
+}
+
+// validation angle: w of qhat * truth^-1 (xyzw) = ip / |t|^2 in fp32, clipped; in double 2 acos(w) (0 where sqrt(1 - w^2) == 0),
+// wrapped to [-pi, pi]; |.|.  The fp32 clip drops a NaN (fmaxf(NaN, -1) = -1 -> angle 0); *w_raw is the unclipped value for the
+// caller that has to tell.
+__device__ __forceinline__ double pose_val_angle(float ip, const float* __restrict__ t, float* w_raw) {
+    const float tt = t[3] * t[3] + t[4] * t[4] + t[5] * t[5] + t[6] * t[6];
+    float w = ip / tt;
+    if (w_raw) *w_raw = w;
+    w = fminf(fmaxf(w, -1.f), 1.f);
+    double ang = 0.0;
+    if (sqrt(1.0 - (double)w * (double)w) != 0.0) ang = 2.0 * acos((double)w);
+    if (ang > 3.14159265358979323846) ang -= 2.0 * 3.14159265358979323846;
+    return fabs(ang);
+}
+
+// ---------------------------------------------------------------------------------------------
 // PoseDistanceLoss forward + gradient + validation metrics in one launch (single block).
 // reference: models/losses.py:47-128.  metric: 0 l2, 1 l1, 2 linf, 3 combined; mode: 0 position, 1 pose.
 // out[0] = loss, out[1] = sum_i sqrt(|dp_i|^2 + eps) (val position error), out[2] = sum_i |angle_i| (val orientation error)
@@ -423,9 +457,9 @@ __global__ __launch_bounds__(256) void pose_loss_kernel(const float* __restrict_
         const float* p = pred + i * 7;
         const float* t = truth + i * 7;
         float d[3], ad[3], g[7];
-        float sq = 0.f;
+        const float sq = pose_pos_sq(p, t, d);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { d[k] = p[k] - t[k]; ad[k] = fabsf(d[k]); sq += d[k] * d[k]; g[k] = 0.f; }
+        for (int k = 0; k < 3; ++k) { ad[k] = fabsf(d[k]); g[k] = 0.f; }
         const float l2 = sqrtf(sq + eps);
         float pos = 0.f;
         if (metric == 0 || metric == 3) {
@@ -446,10 +480,9 @@ __global__ __launch_bounds__(256) void pose_loss_kernel(const float* __restrict_
             g[am] += (d[am] > 0.f) ? 1.f : ((d[am] < 0.f) ? -1.f : 0.f);
         }
         // quaternion part: qhat = q / |q| (no eps: an all-zero quaternion yields NaN, as in the reference)
-        const float q0 = p[3], q1 = p[4], q2 = p[5], q3 = p[6];
-        const float mag = sqrtf(q0 * q0 + q1 * q1 + q2 * q2 + q3 * q3);
-        const float h0 = q0 / mag, h1 = q1 / mag, h2 = q2 / mag, h3 = q3 / mag;
-        const float ip = h0 * t[3] + h1 * t[4] + h2 * t[5] + h3 * t[6];
+        float h[4], mag;
+        const float ip = pose_unit_quat(p, t, h, mag);
+        const float h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3];
         float ori = 0.f;
         float gh[4] = {0.f, 0.f, 0.f, 0.f};  // dL/d qhat
         if (mode == 1) {
@@ -474,14 +507,7 @@ __global__ __launch_bounds__(256) void pose_loss_kernel(const float* __restrict_
         }
         l_acc += (double)pos + (double)alpha * (double)ori;
         p_acc += (double)l2;
-        // validation angle: w of qhat * truth^-1 (xyzw), clipped; 2 acos(w) wrapped to [-pi, pi]; |.|
-        const float tt = t[3] * t[3] + t[4] * t[4] + t[5] * t[5] + t[6] * t[6];
-        float w = ip / tt;
-        w = fminf(fmaxf(w, -1.f), 1.f);
-        double ang = 0.0;
-        if (sqrt(1.0 - (double)w * (double)w) != 0.0) ang = 2.0 * acos((double)w);
-        if (ang > 3.14159265358979323846) ang -= 2.0 * 3.14159265358979323846;
-        a_acc += fabs(ang);
+        a_acc += pose_val_angle(ip, t, nullptr);
     }
     l_acc = wave_sum_d(l_acc); p_acc = wave_sum_d(p_acc); a_acc = wave_sum_d(a_acc);
     if ((threadIdx.x & 63) == 0) { const int wv = threadIdx.x >> 6; red[0][wv] = l_acc; red[1][wv] = p_acc; red[2][wv] = a_acc; }
@@ -490,6 +516,82 @@ __global__ __launch_bounds__(256) void pose_loss_kernel(const float* __restrict_
         out[0] = scale * (float)(red[0][0] + red[0][1] + red[0][2] + red[0][3]);
         out[1] = (float)(red[1][0] + red[1][1] + red[1][2] + red[1][3]);
         out[2] = (float)(red[2][0] + red[2][1] + red[2][2] + red[2][3]);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Per-sample validation errors (the "val" branch of PoseDistanceLoss, one sample per thread, grid-stride):
+// pos_err[i] = sqrt(|dp_i|^2 + eps), ori_err[i] = |angle_i|, pose_unit[i] = (position, q / |q|).
+// A NaN w (all-zero predicted quaternion) stays NaN, as np.clip / np.arccos keep it in the reference.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void pose_errors_kernel(const float* __restrict__ pred, const float* __restrict__ truth, long n, float eps,
+                                                         float* __restrict__ pos_err, float* __restrict__ ori_err, float* __restrict__ pose_unit) {
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
+        const float* p = pred + i * 7;
+        const float* t = truth + i * 7;
+        float d[3], h[4], mag, w;
+        const float sq = pose_pos_sq(p, t, d);
+        const float ip = pose_unit_quat(p, t, h, mag);
+        const double ang = pose_val_angle(ip, t, &w);
+        pos_err[i] = sqrtf(sq + eps);
+        ori_err[i] = (w != w) ? w : (float)ang;
+        if (pose_unit) {
+            float* u = pose_unit + i * 7;
+            u[0] = p[0]; u[1] = p[1]; u[2] = p[2];
+            u[3] = h[0]; u[4] = h[1]; u[5] = h[2]; u[6] = h[3];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Statistics of an [E][T] fp32 error table in fp64, one workgroup, no atomics: every sum is taken in one fixed order, so two
+// calls agree bit for bit.  out = { mean, population std, max, sum[E], mean[E] }.  Two passes like np.std: the mean first, then
+// the squared deviations from it.  NaN propagates into every figure it takes part in (the max included).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ double nan_max_d(double a, double b) { return (a != a) ? a : ((b != b) ? b : (a > b ? a : b)); }
+
+// sum over the block, the same value in every thread: lanes by the xor butterfly, then the four waves in index order
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+    v = wave_sum_d(v);
+    __syncthreads();   // (red may still be read from the previous use)
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__global__ __launch_bounds__(256) void error_stats_kernel(const float* __restrict__ err, int E, int T, double* __restrict__ out) {
+    __shared__ double red[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long total = (long)E * T;
+    double* row_sum = out + 3;
+    double* row_mean = out + 3 + E;
+    // per-episode sums: one wave per row, lanes stride over its T steps
+    for (int e = wv; e < E; e += 4) {
+        double s = 0.0;
+        for (int t = lane; t < T; t += 64) s += (double)err[(long)e * T + t];
+        s = wave_sum_d(s);
+        if (lane == 0) { row_sum[e] = s; row_mean[e] = s / (double)T; }
+    }
+    __syncthreads();   // the row sums just stored are read back below by other threads of this workgroup
+    double s = 0.0;
+    for (int e = threadIdx.x; e < E; e += 256) s += row_sum[e];
+    const double mean = block_sum_d(s, red) / (double)total;
+    double q = 0.0, m = -INFINITY;
+    for (long i = threadIdx.x; i < total; i += 256) {
+        const double x = (double)err[i];
+        const double dv = x - mean;
+        q += dv * dv;
+        m = nan_max_d(m, x);
+    }
+    q = block_sum_d(q, red);
+    for (int o = 32; o > 0; o >>= 1) m = nan_max_d(m, __shfl_xor(m, o));
+    __syncthreads();
+    if (lane == 0) red[wv] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out[0] = mean;
+        out[1] = sqrt(q / (double)total);
+        out[2] = nan_max_d(nan_max_d(red[0], red[1]), nan_max_d(red[2], red[3]));
     }
 }
 
@@ -899,6 +1001,22 @@ int rpe_pose_loss(const float* pred, const float* truth, long n, int metric, int
     if (metric < 0 || metric > 3 || mode < 0 || mode > 1) return rpe_set_error(RPE_ERR_SHAPE, "pose_loss: invalid metric/mode");
     if (n <= 0) return rpe_set_error(RPE_ERR_SHAPE, "pose_loss: empty batch");
     hipLaunchKernelGGL(pose_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pred, truth, n, metric, mode, scale, alpha, eps, out3, grad);
+    RPE_CHECK_LAUNCH();
+    return 0;
+}
+
+int rpe_pose_errors(const float* pred, const float* truth, long n, float eps, float* pos_err, float* ori_err, float* pose_unit, void* stream) {
+    if (n <= 0) return rpe_set_error(RPE_ERR_SHAPE, "pose_errors: empty batch");
+    if (!pred || !truth || !pos_err || !ori_err) return rpe_set_error(RPE_ERR_SHAPE, "pose_errors: pred, truth, pos_err and ori_err are required");
+    hipLaunchKernelGGL(pose_errors_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, pred, truth, n, eps, pos_err, ori_err, pose_unit);
+    RPE_CHECK_LAUNCH();
+    return 0;
+}
+
+int rpe_error_stats(const float* err, int E, int T, double* out, void* stream) {
+    if (E <= 0 || T <= 0) return rpe_set_error(RPE_ERR_SHAPE, "error_stats: E and T must be positive");
+    if (!err || !out) return rpe_set_error(RPE_ERR_SHAPE, "error_stats: err and out are required");
+    hipLaunchKernelGGL(error_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, err, E, T, out);
     RPE_CHECK_LAUNCH();
     return 0;
 }

@@ -245,6 +245,29 @@ class PoseModelBase(nn.Module):
             outs = self._forward_impl(img, depth, x0bar, save=False)
         return outs if len(outs) > 1 else outs[0]
 
+    def _forward_impl(self, img, depth, x0bar, save):
+        """trunk + early-feature heads into the feature rows, then the model's own heads on those rows"""
+        lead, img, depth, x0bar = self._flat_inputs(img, depth, x0bar)
+        return self._heads_fwd(self._feature_rows(img, depth, save), lead, x0bar, save)
+
+    def features_only(self, img, depth):
+        """The measurement-independent half of an inference forward: (lead, rows) with lead = (S, N) or (N,) and rows the fused
+        feature rows of all frames, for `heads_only`.  The rows can serve several measurement vectors (util.learn_utils
+        .evaluate_episodes scores one trunk pass under several noise scales)."""
+        self._materialize(img.device)
+        img = img.contiguous() if img.dtype == torch.uint8 else img.contiguous().float()
+        with torch.no_grad():
+            lead, img, depth, _ = self._flat_inputs(img, depth, None)
+            return lead, self._feature_rows(img, depth, save=False)
+
+    def heads_only(self, rows, lead, self_measurement):
+        """The rest of that forward: `rows` as `features_only` lays them out (one row per frame, time-major) -> the model's outputs.
+        The rows' measurement columns, where the model has them, are written in place."""
+        x0bar = None if self_measurement is None else self_measurement.contiguous().float().reshape(-1, 7)
+        with torch.no_grad():
+            outs = self._heads_fwd(rows, tuple(lead), x0bar, save=False)
+        return outs if len(outs) > 1 else outs[0]
+
     def _features_fwd(self, img, depth, rows, save):
         """img (B,3,H,W); rows [B, ld] fp32: columns [0,L) <- ResNet latent, [L, L+aux) <- aux head."""
         # the bn1 head of a training forward rides on the engine's stem pass (headops.AuxHeadOp.bind_fused): it is bound before the run

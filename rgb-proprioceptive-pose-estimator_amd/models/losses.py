@@ -65,6 +65,13 @@ class PoseDistanceLoss(nn.Module):
         out3, _ = ops.pose_loss(p, t, _METRIC_CODE[self.distance_metric], 0, 1.0, 0.0, self.epsilon, want_grad=False)
         return out3[0], out3[2]
 
+    def per_sample(self, prediction, truth):
+        """(pos_err, ori_err) of every sample as device tensors of shape prediction.shape[:-1]: the "val" quantities before the sum
+        (position distance sqrt(|dp|^2 + epsilon) in metres, |angle| in radians).  Nothing is synchronised."""
+        p, t = self._prep(prediction.detach(), truth)
+        pos, ori, _ = ops.pose_errors(p, t, float(self.epsilon), want_pose=False)
+        return pos, ori
+
     def forward(self, prediction, truth):
         """prediction (*, 7) = (x,y,z,i,j,k,w) with an UNNORMALISED quaternion; truth (*, 7) with a unit, w >= 0 quaternion."""
         if self.mode == "val":

@@ -40,15 +40,21 @@ class NaiveEndEffectorStateEstimator(PoseModelBase):
         """img (N,3,H,W), depth ignored, self_measurement (N,7) -> (pre_out (N,7), post_out (N,7))"""
         return self._call(img, depth, self_measurement)
 
-    def _forward_impl(self, img, depth, x0bar, save):
-        n, L = img.shape[0], self.latent_dim
-        feat = new_rows(n, L, img.device)
+    def _flat_inputs(self, img, depth, x0bar):
+        return (img.shape[0],), img, None, x0bar
+
+    def _feature_rows(self, img, depth, save):
+        feat = new_rows(img.shape[0], self.latent_dim, img.device)
         self._features_fwd(img, None, feat, save)
+        return feat
+
+    def _heads_fwd(self, feat, lead, x0bar, save):
+        n, L = feat.shape[0], self.latent_dim
         h = feat
         for op in self._pre_ops:
             h = op.fwd(h, save=save)
         pre = h
-        post_in = new_rows(n, L + 7, img.device)
+        post_in = new_rows(n, L + 7, feat.device)
         ops.copy2d(feat, post_in, cols=L)
         ops.copy2d((pre - x0bar).contiguous(), post_in[:, L:], cols=7)
         h = post_in
@@ -111,10 +117,16 @@ class NaiveObjectStateEstimator(PoseModelBase):
         """img (N,3,H,W), depth (N,1,H,W) (read only when use_depth), self_measurement (N,7) -> (N,7)"""
         return self._call(img, depth, self_measurement)
 
-    def _forward_impl(self, img, depth, x0bar, save):
-        n = img.shape[0]
-        rows = new_rows(n, self.input_dim, img.device)
+    def _flat_inputs(self, img, depth, x0bar):
+        return (img.shape[0],), img, depth, x0bar
+
+    def _feature_rows(self, img, depth, save):
+        rows = new_rows(img.shape[0], self.input_dim, img.device)
         self._features_fwd(img, depth, rows, save)
+        return rows
+
+    def _heads_fwd(self, rows, lead, x0bar, save):
+        n = rows.shape[0]
         if self.use_proprioception:
             ops.copy2d(x0bar.reshape(n, 7), rows[:, self.latent_dim + self.aux_latent_dim:], cols=7)
         h = rows

@@ -29,6 +29,10 @@ class _SequenceModel(PoseModelBase):
             depth = None
         return S, N, img, depth, None if x0bar is None else x0bar.reshape(S * N, 7)
 
+    def _flat_inputs(self, img, depth, x0bar):
+        S, N, img, depth, x0bar = self._seq_inputs(img, depth, x0bar)
+        return (S, N), img, depth, x0bar
+
     def _state(self, name, n, hid, device):
         """carried (h, c) in rollout mode, None (zero start) otherwise.  The state tensors are PERSISTENT (updated in place by
         _keep): a frame captured into a hipGraph (util.learn_utils.GraphedRolloutFrame) reads and writes fixed addresses."""
@@ -92,11 +96,13 @@ class TemporallyDependentStateEstimator(_SequenceModel):
         """img (S,N,3,H,W), depth (S,N,1,H,W), self_measurement (S,N,7) -> (pre_out, post_out), each (S,N,7)"""
         return self._call(img, depth, self_measurement)
 
-    def _forward_impl(self, img, depth, x0bar, save):
-        S, N, img, depth, x0bar = self._seq_inputs(img, depth, x0bar)
-        dev, F = img.device, self._fdim
-        rows = new_rows(S * N, F, dev)
+    def _feature_rows(self, img, depth, save):
+        rows = new_rows(img.shape[0], self._fdim, img.device)
         self._features_fwd(img, depth, rows, save)
+        return rows
+
+    def _heads_fwd(self, rows, lead, x0bar, save):
+        (S, N), dev, F = lead, rows.device, self._fdim
         h0, c0 = self._state("pre", N, self.pre_measurement_hidden_dim, dev)
         hp, hc = self._pre_rnn.fwd(rows, S, N, h0, c0, save=save)
         self._keep("pre", hc)
@@ -165,11 +171,13 @@ class TemporallyDependentObjectStateEstimator(_SequenceModel):
         """img (S,N,3,H,W), depth (S,N,1,H,W), self_measurement (S,N,7) -> (S,N,7)"""
         return self._call(img, depth, self_measurement)
 
-    def _forward_impl(self, img, depth, x0bar, save):
-        S, N, img, depth, x0bar = self._seq_inputs(img, depth, x0bar)
-        dev = img.device
-        rows = new_rows(S * N, self.input_dim, dev)
+    def _feature_rows(self, img, depth, save):
+        rows = new_rows(img.shape[0], self.input_dim, img.device)
         self._features_fwd(img, depth, rows, save)
+        return rows
+
+    def _heads_fwd(self, rows, lead, x0bar, save):
+        (S, N), dev = lead, rows.device
         if self.use_proprioception:
             ops.copy2d(x0bar, rows[:, self.latent_dim + self.aux_latent_dim:], cols=7)
         h0, c0 = self._state("rnn", N, self.hidden_dim, dev)
@@ -222,12 +230,14 @@ class TemporallyDependentObjectStateEstimatorV2(_SequenceModel):
         """img (S,N,3,H,W), depth (S,N,1,H,W), self_measurement (S,N,7) -> (S,N,7)"""
         return self._call(img, depth, self_measurement)
 
-    def _forward_impl(self, img, depth, x0bar, save):
-        S, N, img, depth, x0bar = self._seq_inputs(img, depth, x0bar)
-        dev = img.device
-        Hi, Hp = self.img_hidden_dim, self.proprio_hidden_dim
-        rows = new_rows(S * N, self.input_dim, dev)
+    def _feature_rows(self, img, depth, save):
+        rows = new_rows(img.shape[0], self.input_dim, img.device)
         self._features_fwd(img, depth, rows, save)
+        return rows
+
+    def _heads_fwd(self, rows, lead, x0bar, save):
+        (S, N), dev = lead, rows.device
+        Hi, Hp = self.img_hidden_dim, self.proprio_hidden_dim
         h0, c0 = self._state("img", N, Hi, dev)
         hi, hc = self._img_rnn.fwd(rows, S, N, h0, c0, save=save)
         self._keep("img", hc)

@@ -580,6 +580,32 @@ def pose_loss(pred, truth, metric, mode, scale, alpha, eps, want_grad=True):
     return out3, grad
 
 
+def pose_errors(pred, truth, eps, want_pose=True):
+    """pred/truth (..., 7) fp32 contiguous -> (pos_err (...), ori_err (...), pose_unit (..., 7) or None): the "val" errors of every
+    sample, and the prediction with its quaternion normalised (rpe_pose_errors).  Enqueued on the current stream; nothing is read back."""
+    if pred.shape != truth.shape or pred.dim() < 1 or pred.shape[-1] != 7:
+        raise ValueError("pose_errors: pred and truth must both be (..., 7), got %s and %s" % (tuple(pred.shape), tuple(truth.shape)))
+    if pred.dtype != torch.float32 or truth.dtype != torch.float32:
+        raise TypeError("pose_errors: pred and truth must be fp32")
+    lead = tuple(pred.shape[:-1])
+    pos = torch.empty(lead, dtype=torch.float32, device=pred.device)
+    ori = torch.empty(lead, dtype=torch.float32, device=pred.device)
+    pose = torch.empty_like(pred) if want_pose else None
+    lib.rpe_pose_errors(_p(_chk(pred, "pred")), _p(_chk(truth, "truth")), pred.numel() // 7, eps, _p(pos), _p(ori), _p(pose), _stream())
+    return pos, ori, pose
+
+
+def error_stats(err):
+    """err (E, T) fp32 contiguous -> fp64 device tensor of 3 + 2 E values: [mean, population std, max, sum[E], mean[E]]
+    (rpe_error_stats: fixed-order fp64 sums, bitwise repeatable, NaN propagates)."""
+    if err.dim() != 2 or err.dtype != torch.float32:
+        raise ValueError("error_stats: err must be an fp32 (E, T) tensor, got %s %s" % (err.dtype, tuple(err.shape)))
+    e, t = err.shape
+    out = torch.empty(3 + 2 * e, dtype=torch.float64, device=err.device)
+    lib.rpe_error_stats(_p(_chk(err, "err")), e, t, _p(out), _stream())
+    return out
+
+
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step):
     lib.rpe_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, step, _stream())
 

@@ -14,6 +14,7 @@ ResNet; models/losses.py:114-128 is the loss; util/learn_utils.py:152-184 the st
     rpe::bn_apply                                   BatchNorm's affine map (+ residual) (+ ReLU) on an NHWC tensor
     rpe::linear_fwd                                 F.linear (+ ReLU)
     rpe::pose_loss / pose_distance_loss             PoseDistanceLoss (raw three-value form / differentiable scalar)
+    rpe::pose_errors                                its "val" branch per sample: position error, |angle| error, unit-quaternion pose
     rpe::adam_step                                  torch.optim.Adam's update of one flat fp32 tensor, in place
 
 Importing this module needs torch only; the HIP library is loaded on the first call (ops.py), so the schemas can be inspected on a
@@ -26,7 +27,7 @@ import torch
 __all__ = ["NAMES"]
 
 _NS = "rpe"
-NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "adam_step")
+NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step")
 
 
 def _ops():
@@ -160,6 +161,18 @@ def _pdl_backward(ctx, dloss, _dgrad):
 
 
 pose_distance_loss.register_autograd(_pdl_backward, setup_context=_pdl_setup)
+
+
+@torch.library.custom_op(_NS + "::pose_errors", mutates_args=(), device_types="cuda")
+def pose_errors(pred: torch.Tensor, truth: torch.Tensor, eps: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """pred, truth (n, 7) fp32 -> (position error (n,), |angle| error in radians (n,), pred with a unit quaternion (n, 7)): the "val" mode of PoseDistanceLoss per sample"""
+    pos, ori, pose = _ops().pose_errors(pred, truth, eps, want_pose=True)
+    return pos, ori, pose
+
+
+@pose_errors.register_fake
+def _(pred, truth, eps):
+    return pred.new_empty(pred.shape[:-1]), pred.new_empty(pred.shape[:-1]), torch.empty_like(pred)
 
 
 # ---- Adam ------------------------------------------------------------------------------------------------------------------------

@@ -9,7 +9,9 @@ Same signature, phases, criterion dict, statistics and checkpoint naming as trai
     synchronises twice per step: models/losses.py:99-113 and util/learn_utils.py:182);
   * with torch.distributed initialised, episodes are sharded over ranks and the flat gradient buffer is
     SUM-all-reduced (RCCL) between backward and the optimizer step.
-rollout() of the reference needs the simulator and is out of scope.
+rollout() of the reference needs the simulator and is out of scope; its model side -- every episode
+walked step by step, per-step position / orientation errors, their per-episode and overall statistics (util/learn_utils.py:
+446-538) -- is `evaluate_episodes`: all episodes advance together as lanes of one batch and the errors stay on the device.
 """
 import copy
 import os
@@ -206,6 +208,173 @@ class GraphedRolloutFrame:
             self.depth.copy_(depth, non_blocking=True)
         self.graph.replay()
         return self.out
+
+
+def eval_chunk_length(max_frames, num_episodes):
+    """timesteps per evaluator call: as many as keep one trunk batch within `max_frames` frames, at least one"""
+    return max(1, int(max_frames) // int(num_episodes))
+
+
+def sweep_measurements(x0, noise_scales, z):
+    """x0 (..., 7) true poses, z a standard-normal draw of that shape -> (K, ..., 7): x0 + sqrt(s_k) z with the quaternion part
+    renormalised, as RecordedEpisodeDataset.refresh_data makes a measurement (util/data_utils.py:162-167 of the reference).  The ONE
+    draw serves every scale, so the scales differ in nothing but the scale; s = 0 gives the true pose back."""
+    out = []
+    for s in noise_scales:
+        xb = x0 + (float(s) ** 0.5) * z
+        out.append(torch.cat([xb[..., :3], xb[..., 3:] / xb[..., 3:].norm(dim=-1, keepdim=True)], dim=-1))
+    return torch.stack(out, 0)
+
+
+def sweep_draw(num_episodes, horizon, noise_seed):
+    """the (E, T, 7) standard-normal draw of a noise sweep (host generator, so a seed means the same numbers on every box)"""
+    return torch.randn((int(num_episodes), int(horizon), 7), generator=torch.Generator().manual_seed(int(noise_seed)))
+
+
+class EpisodeEvaluation:
+    """What `evaluate_episodes` returns.  Device tensors, episode-major, with a leading K dimension when noise scales were swept:
+        outputs (E, T, 7) raw model outputs        poses (E, T, 7) the same with a unit quaternion
+        pos_err (E, T) metres                      ori_err (E, T) radians
+        measurements (E, T, 7) what the heads were given as the own end-effector pose; truth (E, T, 7) the scored poses (no K)
+    and host numbers (numpy float64; scalars, or (K,) in a sweep) read back in one transfer:
+        pos_mean pos_std pos_max ori_mean ori_std ori_max, and per episode (E,) / (K, E): pos_episode_sum pos_episode_mean
+        ori_episode_sum ori_episode_mean.
+    `stats` is the raw table they are views of: (K, 2, 3 + 2 E) = [scale][pos | ori][rpe_error_stats layout]."""
+
+    def __init__(self, outputs, poses, pos_err, ori_err, stats, noise_scales=None, truth=None, measurements=None):
+        stats = np.asarray(stats, dtype=np.float64)
+        self.noise_scales = None if noise_scales is None else [float(s) for s in noise_scales]
+        k = 1 if noise_scales is None else len(self.noise_scales)
+        e = (stats.shape[-1] - 3) // 2
+        if stats.shape != (k, 2, 3 + 2 * e):
+            raise ValueError("stats must be (K, 2, 3 + 2 E); got %r for K = %d" % (stats.shape, k))
+        self.outputs, self.poses, self.pos_err, self.ori_err, self.stats = outputs, poses, pos_err, ori_err, stats
+        self.truth, self.measurements = truth, measurements
+        pick = (lambda a: a[0]) if noise_scales is None else (lambda a: a)
+        for i, name in enumerate(("pos", "ori")):
+            setattr(self, name + "_mean", pick(stats[:, i, 0]))
+            setattr(self, name + "_std", pick(stats[:, i, 1]))
+            setattr(self, name + "_max", pick(stats[:, i, 2]))
+            setattr(self, name + "_episode_sum", pick(stats[:, i, 3:3 + e]))
+            setattr(self, name + "_episode_mean", pick(stats[:, i, 3 + e:]))
+
+    def summary(self):
+        """The lines rollout() of the reference prints (util/learn_utils.py:527-538): one per episode, then the evaluation totals; in a
+        sweep, that block once per noise scale under a line naming the scale."""
+        lines = []
+        for k in range(self.stats.shape[0]):
+            if self.noise_scales is not None:
+                lines.append("noise scale {:g}:".format(self.noise_scales[k]))
+            (pm, ps, _), (om, os_, _) = self.stats[k, 0, :3], self.stats[k, 1, :3]
+            e = (self.stats.shape[-1] - 3) // 2
+            for ep in range(e):
+                lines.append("EPISODE COMPLETED -- Total Pos/Ori err: {:.3f} m / {:.3f} rad, Per-Step Err: {:.3f} m / {:.3f} rad".format(
+                    self.stats[k, 0, 3 + ep], self.stats[k, 1, 3 + ep], self.stats[k, 0, 3 + e + ep], self.stats[k, 1, 3 + e + ep]))
+            lines += ["", "*" * 90,
+                      "EVALUATION COMPLETED -- Per-Step Pos Mean/Std Err: {:.5f} / {:.5f} m || Ori Mean/Std Err: {:.5f} / {:.5f} rad".format(pm, ps, om, os_),
+                      "*" * 90]
+        return "\n".join(lines)
+
+
+def _repeat_rows(rows, lead, k):
+    """feature rows of one trunk pass -> the rows of k copies of every lane: (S, N) lanes become (S, k N), scale-major within a
+    timestep; a flat batch (B,) becomes (k B,), scale-major.  Same padded row layout as headops.new_rows."""
+    cols, pad = rows.shape[1], rows.stride(0)
+    if len(lead) == 2:
+        buf = torch.zeros((lead[0], k, lead[1], pad), dtype=torch.float32, device=rows.device)
+        buf[..., :cols].copy_(rows.unflatten(0, tuple(lead)).unsqueeze(1).expand(lead[0], k, lead[1], cols))
+    else:
+        buf = torch.zeros((k, lead[0], pad), dtype=torch.float32, device=rows.device)
+        buf[..., :cols].copy_(rows.unsqueeze(0).expand(k, lead[0], cols))
+    return buf.view(-1, pad)[:, :cols]
+
+
+def evaluate_episodes(model, dataset, num_episodes, params, *, max_frames=256, noise_scales=None, noise_seed=0):
+    """Score `num_episodes` episodes of `dataset` in one batched pass: the model side of the reference's rollout()
+    (util/learn_utils.py:322-323,342,446-538) without its frame-at-a-time walk.  The E episodes advance together as E lanes,
+    S = max(1, max_frames // E) timesteps per call (one trunk batch of S E frames; BN is folded in eval mode, so frames are
+    independent, and in rollout mode the LSTM state is carried per lane between calls); models without a sequence take the S E
+    frames as one flat batch.  The truth is `obj` for a model with `object_name`, otherwise `x1` against the last output, as in
+    train().  Outputs go episode-major into one (E, T, 7) device buffer; after the last chunk ONE rpe_pose_errors launch gives the
+    per-step errors, two rpe_error_stats launches their statistics, and one device -> host copy reads the scalars.
+    noise_scales=[s_0 .. s_{K-1}]: the same frames scored under K measurement-noise scales -- the trunk runs ONCE per chunk, the heads
+    run with K E lanes on the feature rows repeated K times and measurements `sweep_measurements(x0, scales, z)` with
+    z = sweep_draw(E, T, noise_seed); every field of the result gains a leading K dimension.
+    Single process, device only (no CPU fallback).  model.training / model.rollout are restored and the carried state is reset."""
+    from .. import ops
+    if dist.is_initialized() and dist.get_world_size() > 1:
+        raise RuntimeError("evaluate_episodes is single-process")
+    p0 = next(model.parameters())
+    if not torch.cuda.is_available() or not p0.is_cuda:
+        raise RuntimeError("evaluate_episodes(): the pose models run on the MI355X HIP path only (call model.cuda() first); there is no CPU fallback")
+    E = int(num_episodes)
+    scales = None if noise_scales is None else [float(s) for s in noise_scales]
+    if scales is not None and (not scales or min(scales) < 0):
+        raise ValueError("noise_scales must be a non-empty list of non-negative variances; got %r" % (noise_scales,))
+    K = 1 if scales is None else len(scales)
+    scores_obj = hasattr(model, "object_name")
+    use_depth = model.use_depth if hasattr(model, "use_depth") else False
+    if (scores_obj and getattr(dataset, "obj_name", "") is None) or (not scores_obj and not getattr(dataset, "is_two_arm", True)):
+        raise ValueError("the dataset has no {} poses to score this model against".format("object" if scores_obj else "second-arm"))
+    was_training, was_rollout = model.training, model.rollout
+    dataset.refresh_data(E, params["camera_name"], params["noise_scale"])
+    T = len(dataset)
+    S = eval_chunk_length(max_frames, E)
+    dev = p0.device
+    outputs = torch.empty((K, E, T, 7), dtype=torch.float32, device=dev)
+    truth = torch.empty((E, T, 7), dtype=torch.float32, device=dev)
+    meas = torch.empty((K, E, T, 7), dtype=torch.float32, device=dev)
+    z = None if scales is None else sweep_draw(E, T, noise_seed).to(dev)
+    # The K E lanes get state tensors of their own: the module's carried (h, c) stay where they are -- a frame captured earlier
+    # (GraphedRolloutFrame) has their addresses baked in -- and come back, zeroed, afterwards.
+    carried = getattr(model, "_carried", None)
+    if carried is not None:
+        model._carried = {}
+    model.eval()
+    model.rollout = True
+    model.reset_initial_state(K * E)
+    try:
+        with torch.no_grad():
+            t0 = 0
+            for img, depth, x0bar, x0, x1, obj in _chunks(dataset, T, S, use_depth):
+                s = img.shape[0]
+                target = obj if scores_obj else x1
+                if target is None:
+                    raise ValueError("the dataset has no {} poses for this model".format("object" if scores_obj else "second-arm"))
+                truth[:, t0:t0 + s].copy_(target.transpose(0, 1))
+                seq = model.requires_sequence
+                if not seq:   # S E independent frames: one flat batch
+                    img = img.reshape(s * E, *img.shape[2:])
+                    depth = None if depth is None else depth.reshape(s * E, *depth.shape[2:])
+                # measurements of this chunk, (K, s, E, 7): the dataset's, or the sweep's own
+                xk = x0bar.unsqueeze(0) if scales is None else sweep_measurements(x0, scales, z[:, t0:t0 + s].transpose(0, 1))
+                meas[:, :, t0:t0 + s].copy_(xk.transpose(1, 2))
+                if scales is None:
+                    out = model(img, depth, x0bar if seq else x0bar.reshape(s * E, 7))
+                    out = out[-1] if isinstance(out, tuple) else out
+                    outputs[0, :, t0:t0 + s].copy_(out.reshape(s, E, 7).transpose(0, 1))
+                else:
+                    lead, rows = model.features_only(img, depth)
+                    if seq:   # lanes of a timestep: scale-major (k, e)
+                        out = model.heads_only(_repeat_rows(rows, lead, K), (s, K * E), xk.permute(1, 0, 2, 3))
+                        out = (out[-1] if isinstance(out, tuple) else out).reshape(s, K, E, 7).permute(1, 2, 0, 3)
+                    else:
+                        out = model.heads_only(_repeat_rows(rows, lead, K), (K * s * E,), xk)
+                        out = (out[-1] if isinstance(out, tuple) else out).reshape(K, s, E, 7).permute(0, 2, 1, 3)
+                    outputs[:, :, t0:t0 + s].copy_(out)
+                t0 += s
+            pos, ori, poses = ops.pose_errors(outputs, truth.unsqueeze(0).expand(K, E, T, 7).contiguous(), 1e-4, want_pose=True)
+            stats = torch.stack([torch.stack([ops.error_stats(pos[k]), ops.error_stats(ori[k])]) for k in range(K)])
+            stats = stats.cpu().numpy()   # the one device -> host read of the evaluation
+    finally:
+        model.train(was_training)
+        model.rollout = was_rollout
+        if carried is not None:
+            model._carried = carried
+        model.reset_initial_state(E)
+    if scales is None:
+        outputs, poses, pos, ori, meas = outputs[0], poses[0], pos[0], ori[0], meas[0]
+    return EpisodeEvaluation(outputs, poses, pos, ori, stats, scales, truth=truth, measurements=meas)
 
 
 def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_per_epoch, num_val_episodes_per_epoch, params, device,
