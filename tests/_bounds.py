@@ -319,3 +319,225 @@ def assert_unbiased(got, ref, dtype, label, bnd=None):
     print("BIAS  %-48s %+.4f" % (label, b))
     assert abs(b) <= BIAS_TOL, "%s: rounding bias %.3f ulp (round-to-nearest-even gives ~0, truncation ~-0.5)" % (label, b)
     return b
+
+
+# ------------------------------------------------------------------ the fp32 scalar kernels of csrc/heads.hip
+# LSTM cell, PoseDistanceLoss (+ gradient) and Adam are short fp32 formulas per element: no reduction, so no statistics.  Their
+# bound is first-order error propagation through the formula itself, carried along with the fp64 value (class Fx):
+#   - a sum or product adds EW u32 times the magnitudes it combines (as EPI does for a GEMM's epilogue);
+#   - a double constant rounded once to fp32 carries u32 |c|;
+#   - an elementary function f (sigmoid through __expf, tanhf) of z with propagated error dz errs by at most
+#         |f'(z)| dz + TR u32 (1 + |z|) |f'(z)| + EW u32 |f(z)|
+#     "k ulp of the result" is the last term alone and fails in sigmoid's tails: sigmoid(x) = 1 / (1 + __expf(-x)) and __expf(x)
+#     = exp2(x log2 e) rounds its ARGUMENT, a relative error of |x| u32 in the result -- the middle term;
+#   - every bound gets the fp32 floor (the smallest normal: a flushed subnormal is allowed).
+# TR and EW are fixed by tests/test_bounds_cpu.py (test_scalar_kernels_stay_within_half_the_bound) on the very inputs of the GPU
+# tests (tests/_scalar_cases.py) and used unchanged there: the smallest values of 1, 1.5, 2, 3, 4, 6, ... at which torch-fp32
+# statements of the kernels stay at <= 0.5 of every bound, then headroom for __expf.  Worst err/bound on the CPU (worst output first):
+#   EW 1   (TR 1): 1.43   EW 1.5: 0.96   EW 2: 0.76   EW 3: 0.55   -- the activated gates: 1 / (1 + e) near 1 rounds the sum and the
+#   EW 3, TR 1.5: 0.51   EW 3, TR 2: 0.48                             quotient, 1.5 u32 together, whatever the exponential's accuracy
+# so the CPU fixes EW = 3, TR = 2.  torch's CPU exp is < 1 ulp; __expf is documented at 2 ulp plus the argument term.  At z ~ 0,
+# where the exponential's share is largest, one more ulp of e is 2 u32 |f'(z)| more: TR = 2 + 2 = 4.  At TR = 4, EW = 3:
+#   LSTM forward: activated gates 0.48, c 0.25, h 0.21      LSTM backward: dgates i 0.21, f 0.17, g 0.18, o 0.15, dc 0.30
+#   Adam, the kernel's statement: p 0.33, m 0.28, v 0.31    Adam, torch's statement (oracle.adam_update): p 0.33, m 0.33, v 0.30
+#   pose loss: gradient 0.17 (the oracle's loss through fp32 autograd: 0.21), the three sums 0.07
+TR = 4.0
+EW = 3.0
+F32_FLOOR = FLOOR[torch.float32]
+
+
+def _t64(x):
+    return x if torch.is_tensor(x) else torch.tensor(float(x), dtype=torch.float64)
+
+
+class Fx:
+    """An fp64 value v with a bound e on the error of its fp32 evaluation; operators propagate both (first order)."""
+    __slots__ = ("v", "e")
+
+    def __init__(self, v, e=None):
+        self.v = _t64(v)
+        self.e = torch.zeros_like(self.v) if e is None else _t64(e)
+
+    @staticmethod
+    def const(c):
+        """a double that reaches the kernel rounded to fp32"""
+        return Fx(float(c), U32 * abs(float(c)))
+
+    @staticmethod
+    def of(x):
+        return x if isinstance(x, Fx) else Fx(x)
+
+    @staticmethod
+    def where(mask, a, b):
+        return Fx(torch.where(mask, a.v, b.v), torch.where(mask, a.e, b.e))
+
+    @staticmethod
+    def cat(parts, dim):
+        return Fx(torch.cat([p.v for p in parts], dim), torch.cat([p.e for p in parts], dim))
+
+    def __getitem__(self, idx):
+        return Fx(self.v[idx], self.e[idx])
+
+    def __neg__(self):
+        return Fx(-self.v, self.e)
+
+    def abs(self):
+        return Fx(self.v.abs(), self.e)
+
+    def __add__(self, o):
+        o = Fx.of(o)
+        return Fx(self.v + o.v, self.e + o.e + EW * U32 * (self.v.abs() + o.v.abs()))
+
+    __radd__ = __add__
+
+    def __sub__(self, o):
+        o = Fx.of(o)
+        return Fx(self.v - o.v, self.e + o.e + EW * U32 * (self.v.abs() + o.v.abs()))
+
+    def __rsub__(self, o):
+        return Fx.of(o) - self
+
+    def __mul__(self, o):
+        o = Fx.of(o)
+        v = self.v * o.v
+        return Fx(v, self.v.abs() * o.e + o.v.abs() * self.e + self.e * o.e + EW * U32 * v.abs())
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, o):
+        o = Fx.of(o)
+        v = self.v / o.v
+        lo = (o.v.abs() - o.e).clamp_min(1e-300)             # the divisor at its smallest
+        return Fx(v, (self.e + v.abs() * o.e) / lo + EW * U32 * v.abs())
+
+    def sqrt(self):
+        v = self.v.sqrt()
+        return Fx(v, v - (self.v - self.e).clamp_min(0.0).sqrt() + EW * U32 * v)    # concave: the lower end moves further
+
+    def act(self, f, df):
+        """f(z) of an elementary function with derivative df(z, f(z))"""
+        fv = f(self.v)
+        d = df(self.v, fv).abs()
+        return Fx(fv, d * self.e + TR * U32 * (1.0 + self.v.abs()) * d + EW * U32 * fv.abs())
+
+    def sigmoid(self):
+        return self.act(torch.sigmoid, lambda z, s: s * (1.0 - s))
+
+    def tanh(self):
+        return self.act(torch.tanh, lambda z, t: 1.0 - t * t)
+
+    def out(self):
+        """(reference, bound) of a stored fp32 value"""
+        return self.v, self.e + F32_FLOOR
+
+
+def lstm_cell_fwd_ref(gates, b_ih, b_hh, c_prev):
+    """rpe_lstm_cell_fwd in fp64 from its fp32 operands: gates [N, 4 Hd] pre-activations without biases (torch order i, f, g, o),
+    c_prev [N, Hd] or None -> {i, f, g, o (the activated gates written back), c, h: (reference, bound)}.
+    z = g + b_ih + b_hh carries dz = 2 u32 (|g| + |b_ih| + |b_hh|); c = f c_prev + i g; h = o tanh(c)."""
+    n, hd = gates.shape[0], gates.shape[1] // 4
+    g, bi, bh = gates.double().view(n, 4, hd), b_ih.double().view(4, hd), b_hh.double().view(4, hd)
+    z = Fx(g + bi + bh, 2.0 * U32 * (g.abs() + bi.abs() + bh.abs()))
+    i, f, gg, o = z[:, 0].sigmoid(), z[:, 1].sigmoid(), z[:, 2].tanh(), z[:, 3].sigmoid()
+    cp = Fx(torch.zeros_like(i.v) if c_prev is None else c_prev.double())
+    c = f * cp + i * gg
+    h = o * c.tanh()
+    return dict(i=i.out(), f=f.out(), g=gg.out(), o=o.out(), c=c.out(), h=h.out())
+
+
+def lstm_cell_bwd_ref(gates_act, c_prev, c_cur, dh, dc_in):
+    """rpe_lstm_cell_bwd in fp64 from its fp32 operands (the ACTIVATED gates and c of the forward, as the kernel re-reads them)
+    -> {di, df, dg, do (the four dgates blocks), dc (dL/dc_{t-1}): (reference, bound)}."""
+    n, hd = gates_act.shape[0], gates_act.shape[1] // 4
+    a = gates_act.double().view(n, 4, hd)
+    gi, gf, gg, go = Fx(a[:, 0]), Fx(a[:, 1]), Fx(a[:, 2]), Fx(a[:, 3])
+    tc = Fx(c_cur.double()).tanh()
+    dhv = Fx(dh.double())
+    cp = Fx(torch.zeros_like(tc.v) if c_prev is None else c_prev.double())
+    dc = Fx(dc_in.double()) + dhv * go * (1.0 - tc * tc)
+    return dict(di=(dc * gg * gi * (1.0 - gi)).out(), df=(dc * cp * gf * (1.0 - gf)).out(), dg=(dc * gi * (1.0 - gg * gg)).out(),
+                do=(dhv * tc * go * (1.0 - go)).out(), dc=(dc * gf).out())
+
+
+def _sum_cols(x):
+    """x[:, 0] + x[:, 1] + ..., left to right"""
+    s = x[:, 0]
+    for k in range(1, x.v.shape[1]):
+        s = s + x[:, k]
+    return s
+
+
+def _f32(x):
+    """a Python double as the kernel receives it through a float argument"""
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+def pose_loss_ref(pred, truth, metric, mode, scale, alpha, eps):
+    """rpe_pose_loss in fp64 from its fp32 operands (pred / truth [n, 7]; metric 0 l2, 1 l1, 2 linf, 3 combined; mode 0 position,
+    1 pose) -> {grad: (reference [n, 7], bound), out: (reference [3], bound)}.
+    The gradient is per element: EW u32 of the magnitudes combined, with the conditioning of d / l2, 1 / |q| and the projection
+    (gh - qhat <gh, qhat>) / |q| carried by the propagation (where gh is parallel to qhat the difference cancels, and its
+    rounding noise is divided by |q|).  sign, the first maximal index and the clamp's pass-through are decided on the exact fp32
+    differences.  The three sums are accumulated in double by the kernel: the per-sample fp32 bounds added up, plus one fp32
+    rounding of the total (and the product by `scale`).  The validation angle 2 acos(|w|) is bounded at both ends of w's
+    interval (it has no derivative at |w| = 1)."""
+    p, t = pred.double().reshape(-1, 7), truth.double().reshape(-1, 7)
+    n = p.shape[0]
+    scale, alpha, eps = _f32(scale), _f32(alpha), _f32(eps)
+    zero = torch.zeros(n, dtype=torch.float64, device=p.device)
+    d = Fx(p[:, :3]) - Fx(t[:, :3])
+    l2 = (_sum_cols(d * d) + eps).sqrt()
+    ad, sgn = d.abs(), torch.sign(d.v)
+    g, pos = Fx(torch.zeros_like(d.v)), Fx(zero)
+    if metric in (0, 3):
+        pos = pos + l2
+        g = g + d / l2[:, None]
+    if metric in (1, 3):
+        pos = pos + _sum_cols(ad)
+        g = g + Fx(sgn)
+    if metric in (2, 3):
+        am = torch.zeros(n, dtype=torch.long, device=p.device)       # the first maximal index
+        for k in (1, 2):
+            am = torch.where(ad.v[:, k] > ad.v.gather(1, am[:, None])[:, 0], torch.full_like(am, k), am)
+        hot = torch.nn.functional.one_hot(am, 3).double()
+        pos = pos + Fx((ad.v * hot).sum(1), (ad.e * hot).sum(1))
+        g = g + Fx(hot * sgn)
+    q, tq = Fx(p[:, 3:]), Fx(t[:, 3:])
+    mag = _sum_cols(q * q).sqrt()
+    h = q / mag[:, None]
+    ip = _sum_cols(h * tq)
+    ori, gq = Fx(zero), Fx(torch.zeros(n, 4, dtype=torch.float64, device=p.device))
+    if mode == 1:
+        h3 = h[:, 3]
+        ori = (1.0 - ip * ip) + Fx((-h3.v).clamp_min(0.0), h3.e)
+        gh = (ip * -2.0)[:, None] * tq
+        gh3 = Fx.where(p[:, 6] <= 0.0, gh[:, 3] - 1.0, gh[:, 3])       # -qhat_w >= 0: the clamp passes the gradient at the boundary
+        gh = Fx.cat([gh[:, :3], gh3[:, None]], 1)
+        gq = (gh - h * _sum_cols(gh * h)[:, None]) / mag[:, None]
+        gq = gq * (Fx(scale) * alpha)
+    grad = Fx.cat([g * scale, gq], 1)
+    tot = (pos.v + alpha * ori.v).sum()
+    loss = Fx(tot, (pos.e + alpha * ori.e).sum() + U32 * tot.abs()) * scale
+    val_pos = Fx(l2.v.sum(), l2.e.sum() + U32 * l2.v.sum())
+    w = ip / _sum_cols(tq * tq)
+    ang = lambda x: 2.0 * torch.acos(x.clamp(0.0, 1.0))
+    wa = w.v.abs().clamp_max(1.0)
+    a = ang(wa)
+    da = torch.maximum(ang(wa - w.e) - a, a - ang(wa + w.e))
+    val_ori = Fx(a.sum(), da.sum() + U32 * a.sum())
+    out = Fx(torch.stack([loss.v, val_pos.v, val_ori.v]), torch.stack([loss.e, val_pos.e, val_ori.e]))
+    return dict(grad=grad.out(), out=out.out())
+
+
+def adam_ref(p, g, m, v, step, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8):
+    """One Adam step (torch.optim.Adam defaults) in fp64 from the fp32 operands, with the scalars in double as torch forms them
+    (1 - 0.999 is not 1.f - 0.999f) -> {p, m, v: (reference, bound)}.  The propagation follows adam_kernel's statement
+        m' = m + (g - m)(1 - b1);  v' = v b2 + g g (1 - b2);  p' = p - (lr / bc1) (m' / (sqrt(v') / sqrt(bc2) + eps))
+    so m' and v' carry a few EW u32 of the magnitudes of one fused step, and p' carries EW u32 |p| plus the update's own error."""
+    P, G, M, V = Fx(p.double()), Fx(g.double()), Fx(m.double()), Fx(v.double())
+    bc1, bc2s = Fx.const(1.0 - b1 ** step), Fx.const(math.sqrt(1.0 - b2 ** step))
+    M, Mt = M + (G - M) * Fx.const(1.0 - b1), M * Fx.const(b1) + G * Fx.const(1.0 - b1)
+    M = Fx(M.v, torch.maximum(M.e, Mt.e))          # torch's own statement m b1 + g (1 - b1) is as correct: whichever allows more
+    V = V * Fx.const(b2) + G * G * Fx.const(1.0 - b2)
+    upd = (Fx.const(lr) / bc1) * (M / (V.sqrt() / bc2s + Fx.const(eps)))
+    return dict(p=(P - upd).out(), m=M.out(), v=V.out())

@@ -7,11 +7,14 @@
   single-number metric max|got - ref| / max|ref| passes them."""
 import math
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import _bounds as B
+import _scalar_cases as C
+from oracle import pose_oracle as po
 from test_gpu_ops import CONVS
 
 OLD_TOL = {torch.float32: 2e-5, torch.bfloat16: 2e-2, torch.float16: 3e-3}
@@ -292,3 +295,280 @@ def test_gram_stats_bound():
     got = (scale, (beta - mean * scale).float().double(), mean.float().double(), invstd)
     worst = B.assert_gram_stats(got, x.double(), w, gamma, beta, "gram stats")
     assert worst <= 0.5
+
+
+# ------------------------------------------------------------------ the fp32 scalar kernels: LSTM cell, pose loss, Adam
+# Plain torch-fp32 statements of the kernels (from the formulas of oracle/pose_oracle.py: lstm_forward, pose_loss, adam_update), with
+# switches for the faults the bounds must reject.  Each runs on the inputs of the GPU tests (tests/_scalar_cases.py).
+def lstm_fwd_f32(gates, b_ih, b_hh, c_prev, mutant=None):
+    """-> (activated gates [N, 4 Hd], c, h)"""
+    g = gates + b_ih if mutant == "b_hh omitted" else gates + b_ih + b_hh
+    i, f, gg, o = g.chunk(4, dim=-1)
+    if mutant == "f and o swapped":
+        f, o = o, f
+    i, f, gg, o = torch.sigmoid(i), torch.sigmoid(f), torch.tanh(gg), torch.sigmoid(o)
+    cp = torch.zeros_like(i) if c_prev is None or mutant == "c_prev ignored" else c_prev
+    c = f * cp + i * gg
+    return torch.cat([i, f, gg, o], -1), c, o * torch.tanh(c)
+
+
+def lstm_bwd_f32(act, c_prev, c_cur, dh, dc_in, mutant=None):
+    """-> (dgates [N, 4 Hd], dc_out): the five expressions of lstm_cell_bwd_kernel"""
+    gi, gf, gg, go = act.chunk(4, dim=-1)
+    tc = torch.tanh(c_cur)
+    dc = dh * go * (1 - tc * tc)
+    if mutant != "dc_io input dropped":
+        dc = dc_in + dc
+    cp = torch.zeros_like(gi) if c_prev is None or mutant == "c_prev ignored" else c_prev
+    dgg = dc * gi * (gg * (1 - gg) if mutant == "g (1 - g) for the g gate" else 1 - gg * gg)
+    dgo = (dc if mutant == "dg[o] from dc" else dh) * tc * go * (1 - go)
+    dco = dc if mutant == "dc_io written before the f multiply" else dc * gf
+    return torch.cat([dc * gg * gi * (1 - gi), dc * cp * gf * (1 - gf), dgg, dgo], -1), dco
+
+
+LSTM_MUTANTS = ["f and o swapped", "b_hh omitted", "c_prev ignored", "g (1 - g) for the g gate", "dc_io input dropped",
+                "dc_io written before the f multiply", "dg[o] from dc"]
+
+
+def _lstm_ratios(case, mutant=None):
+    """worst err/bound of every output of the fp32 cell statement (forward, then backward from the CORRECT forward's outputs)"""
+    hd = case["gates"].shape[1] // 4
+    act, c, h = lstm_fwd_f32(case["gates"], case["b_ih"], case["b_hh"], case["c_prev"], mutant)
+    ref = B.lstm_cell_fwd_ref(case["gates"], case["b_ih"], case["b_hh"], case["c_prev"])
+    out = {}
+    for k, name in enumerate("ifgo"):
+        out["fwd " + name] = B.check(act[:, k * hd:(k + 1) * hd], *ref[name], name)[1]
+    out["fwd c"], out["fwd h"] = B.check(c, *ref["c"], "c")[1], B.check(h, *ref["h"], "h")[1]
+    act, c, _ = lstm_fwd_f32(case["gates"], case["b_ih"], case["b_hh"], case["c_prev"])
+    dg, dco = lstm_bwd_f32(act, case["c_prev"], c, case["dh"], case["dc_in"], mutant)
+    ref = B.lstm_cell_bwd_ref(act, case["c_prev"], c, case["dh"], case["dc_in"])
+    for k, name in enumerate(("di", "df", "dg", "do")):
+        out["bwd " + name] = B.check(dg[:, k * hd:(k + 1) * hd], *ref[name], name)[1]
+    out["bwd dc"] = B.check(dco, *ref["dc"], "dc")[1]
+    return out
+
+
+def _lstm_cases(n, hd):
+    return [C.lstm_case(n, hd, kind, wp) for kind in C.LSTM_KINDS for wp in (False, True)]
+
+
+def test_lstm_reference_is_the_oracle_cell():
+    """the fp64 references equal one step of oracle.lstm_forward in fp64 and its autograd gradients"""
+    case = C.lstm_case(33, 64, "unit", True)
+    d = {k: v.double() for k, v in case.items()}
+    gates = d["gates"].clone().requires_grad_(True)
+    cp = d["c_prev"].clone().requires_grad_(True)
+    i, f, gg, o = (gates + d["b_ih"] + d["b_hh"]).chunk(4, dim=-1)
+    c = torch.sigmoid(f) * cp + torch.sigmoid(i) * torch.tanh(gg)        # oracle/pose_oracle.py: lstm_forward
+    h = torch.sigmoid(o) * torch.tanh(c)
+    dgates, dcp = torch.autograd.grad([h, c], (gates, cp), [d["dh"], d["dc_in"]])
+    ref = B.lstm_cell_fwd_ref(case["gates"], case["b_ih"], case["b_hh"], case["c_prev"])
+    assert _close(ref["c"][0], c.detach()) and _close(ref["h"][0], h.detach())
+    act = torch.cat([ref[k][0] for k in "ifgo"], -1)
+    rb = B.lstm_cell_bwd_ref(act, d["c_prev"], c.detach(), d["dh"], d["dc_in"])
+    assert _close(torch.cat([rb[k][0] for k in ("di", "df", "dg", "do")], -1), dgates) and _close(rb["dc"][0], dcp)
+
+
+# -- pose loss
+def pose_loss_f32(pred, truth, metric, mode, scale, alpha, eps, mutant=None):
+    """-> (out3 fp32 [loss, val position error, val orientation error], grad [n, 7]); the sums in double, as the kernel takes them"""
+    f = torch.float32
+    p, t = pred.reshape(-1, 7), truth.reshape(-1, 7)
+    n = p.shape[0]
+    scale, alpha, eps = (torch.tensor(x, dtype=f) for x in (scale, alpha, eps))
+    d = p[:, :3] - t[:, :3]
+    ad = d.abs()
+    sgn = torch.where(d == 0, torch.ones_like(d), torch.sign(d)) if mutant == "sign(0) = 1" else torch.sign(d)
+    l2 = torch.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2] + eps)
+    g, pos = torch.zeros(n, 3), torch.zeros(n)
+    if metric in (0, 3):
+        pos, g = pos + l2, g + d / l2[:, None]
+    if metric in (1, 3):
+        pos, g = pos + ((ad[:, 0] + ad[:, 1]) + ad[:, 2]), g + sgn
+    if metric in (2, 3):
+        am = torch.zeros(n, dtype=torch.long)
+        for k in (1, 2):
+            cur = ad.gather(1, am[:, None])[:, 0]
+            am = torch.where(ad[:, k] >= cur if mutant == "linf to the last index" else ad[:, k] > cur, torch.full_like(am, k), am)
+        hot = F.one_hot(am, 3).float()
+        pos, g = pos + (ad * hot).sum(1), g + hot * sgn
+    q, tq = p[:, 3:], t[:, 3:]
+    mag = torch.sqrt(((q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + q[:, 2] * q[:, 2]) + q[:, 3] * q[:, 3])
+    h = q / mag[:, None]
+    ht = h * tq
+    ip = ((ht[:, 0] + ht[:, 1]) + ht[:, 2]) + ht[:, 3]
+    ori, gq = torch.zeros(n), torch.zeros(n, 4)
+    if mode == 1:
+        ori = (1 - ip * ip) + (-h[:, 3]).clamp_min(0)
+        gh = (-2 * ip)[:, None] * tq
+        gh[:, 3] -= (-h[:, 3] >= 0).float()
+        if mutant == "no projection":
+            gq = gh
+        else:
+            x = gh * h
+            hd = ((x[:, 0] + x[:, 1]) + x[:, 2]) + x[:, 3]
+            gq = (gh - h * hd[:, None]) / mag[:, None]
+    grad = torch.cat([(scale * alpha if mutant == "alpha on the position part" else scale) * g, scale * alpha * gq], 1)
+    tt = ((tq[:, 0] * tq[:, 0] + tq[:, 1] * tq[:, 1]) + tq[:, 2] * tq[:, 2]) + tq[:, 3] * tq[:, 3]
+    w = (ip / tt).clamp(-1, 1).double()
+    ang = torch.where(torch.sqrt(1 - w * w) != 0, 2 * torch.acos(w), torch.zeros_like(w))
+    ang = torch.where(ang > np.pi, ang - 2 * np.pi, ang).abs()
+    tot = (pos.double() + alpha.double() * ori.double()).sum()
+    out3 = torch.stack([scale * tot.float(), l2.double().sum().float(), ang.sum().float()])
+    return out3, grad
+
+
+def pose_loss_autograd_f32(pred, truth, metric, mode, scale, alpha, eps):
+    """the oracle's own statement in fp32, differentiated by autograd -> (loss, grad)"""
+    p = pred.clone().requires_grad_(True)
+    loss = po.pose_loss(p, truth, ("l2", "l1", "linf", "combined")[metric], scale, alpha, eps, ("position", "pose")[mode])
+    (grad,) = torch.autograd.grad(loss, p)
+    return loss.detach(), grad
+
+
+POSE_MUTANTS = ["no projection", "alpha on the position part", "linf to the last index", "sign(0) = 1"]
+
+
+def _pose_cases(n):
+    for rot in C.POSE_ROTS:
+        pred, truth = C.pose_rows(n, rot)
+        for metric in C.POSE_METRICS:
+            for mode in C.POSE_MODES:
+                for scale, alpha in C.POSE_SCALES:
+                    yield pred, truth, (metric, mode, scale, alpha, C.POSE_EPS)
+
+
+def test_pose_reference_is_the_oracle_loss():
+    """the fp64 reference equals oracle.pose_loss in fp64 and its autograd gradient, exact rows (ties, zeros, the clamp's edge) included"""
+    for pred, truth, (metric, mode, scale, alpha, eps) in _pose_cases(257):
+        p = pred.double().requires_grad_(True)
+        loss = po.pose_loss(p, truth.double(), ("l2", "l1", "linf", "combined")[metric], scale, alpha, B._f32(eps), ("position", "pose")[mode])
+        (grad,) = torch.autograd.grad(loss, p)
+        ref = B.pose_loss_ref(pred, truth, metric, mode, scale, alpha, eps)
+        assert _close(ref["out"][0][0], loss.detach()), (metric, mode)
+        assert float((ref["grad"][0] - grad).abs().max()) <= 1e-9 * max(1.0, float(grad.abs().max())), (metric, mode)
+    pe, oe = po.pose_loss(pred, truth, mode="val")                  # the validation sums (the oracle's are fp32 / numpy)
+    ref = B.pose_loss_ref(pred, truth, 0, 1, 1.0, 1.0, 1e-4)["out"][0]
+    assert abs(float(ref[1]) - float(pe)) <= 1e-5 * float(pe) and abs(float(ref[2]) - oe) <= 1e-4 * oe
+
+
+# -- Adam
+def adam_f32(p, g, m, v, step, lr, b1, b2, eps, mutant=None):
+    """adam_kernel's statement in torch fp32, scalars formed in double -> (p, m, v)"""
+    f = lambda x: torch.tensor(x, dtype=torch.float32)
+    s = step - 1 if mutant == "bias correction of step s - 1" else step
+    bc1, bc2 = 1.0 - b1 ** s, 1.0 - b2 ** s
+    omb1, omb2 = f(1.0 - b1), f(1.0 - b2)
+    if mutant == "1 - beta in fp32":
+        omb1, omb2 = f(1.0) - f(b1), f(1.0) - f(b2)
+    m = m + ((g * g if mutant == "m updated with g g" else g) - m) * omb1
+    v = v * f(b2) + g * g * omb2
+    if mutant == "eps inside the square root":
+        denom = torch.sqrt(v + f(eps)) / f(math.sqrt(bc2)) if bc2 > 0 else torch.full_like(v, float("inf"))
+    else:
+        with np.errstate(all="ignore"):
+            denom = torch.sqrt(v) / f(bc2 if mutant == "bc2 without the square root" else math.sqrt(bc2)) + f(eps)
+    return p - (f(lr) / f(bc1)) * (m / denom), m, v
+
+
+def adam_torch_f32(p, g, m, v, step, lr, b1, b2, eps):
+    """the oracle's statement (torch.optim.Adam's own operations) on fp32 tensors"""
+    p, m, v = p.clone(), m.clone(), v.clone()
+    po.adam_update(p, g, m, v, step, lr, b1, b2, eps)
+    return p, m, v
+
+
+ADAM_MUTANTS = ["bc2 without the square root", "eps inside the square root", "1 - beta in fp32", "bias correction of step s - 1",
+                "m updated with g g"]
+
+
+def _adam_ratios(fn, case, step, **kw):
+    p, g, m, v = case
+    got = fn(p, g, m, v, step, **C.ADAM_HP, **kw)
+    ref = B.adam_ref(p, g, m, v, step, **C.ADAM_HP)
+    return {k: B.check(t, *ref[k], k)[1] for k, t in zip("pmv", got)}
+
+
+def _adam_cases(n):
+    return [(C.adam_case(n, step, kind), step) for step in C.ADAM_STEPS for kind in C.ADAM_KINDS]
+
+
+def scalar_kernel_ratios():
+    """{group: worst err/bound} of the correct fp32 statements over every listed input"""
+    worst = {}
+
+    def put(group, r):
+        worst[group] = max(worst.get(group, 0.0), r)
+
+    for n, hd in C.LSTM_SHAPES:
+        for case in _lstm_cases(n, hd):
+            for k, r in _lstm_ratios(case).items():
+                put("lstm " + ("fwd gates" if k[4:] in "ifgo" and k.startswith("fwd") else k), r)
+    for n in C.POSE_NS:
+        for pred, truth, args in _pose_cases(n):
+            ref = B.pose_loss_ref(pred, truth, *args)
+            out3, grad = pose_loss_f32(pred, truth, *args)
+            put("pose grad", B.check(grad, *ref["grad"], "grad")[1])
+            put("pose sums", B.check(out3, *ref["out"], "out3")[1])
+            loss, grad = pose_loss_autograd_f32(pred, truth, *args)
+            put("pose grad (autograd)", B.check(grad, *ref["grad"], "grad")[1])
+    for n in C.ADAM_NS:
+        for case, step in _adam_cases(n):
+            for k, r in _adam_ratios(adam_f32, case, step).items():
+                put("adam kernel form " + k, r)
+            for k, r in _adam_ratios(adam_torch_f32, case, step).items():
+                put("adam torch form " + k, r)
+    return worst
+
+
+def test_scalar_kernels_stay_within_half_the_bound():
+    """fixes _bounds.TR and _bounds.EW: correct fp32 statements of the LSTM cell, the pose loss and Adam at <= 0.5 of every bound on
+    every input of the GPU tests"""
+    worst = scalar_kernel_ratios()
+    for k, r in sorted(worst.items()):
+        print("soundness %-28s worst err/bound %.3f" % (k, r))
+    bad = {k: r for k, r in worst.items() if not r <= 0.5}
+    assert not bad, bad
+    assert max(worst.values()) > 0.1, "the bounds are needlessly loose"
+
+
+@pytest.mark.parametrize("n,hd", C.LSTM_SHAPES)
+def test_lstm_mutants_are_rejected(n, hd):
+    for mutant in LSTM_MUTANTS:
+        worst = max(max(_lstm_ratios(case, mutant).values()) for case in _lstm_cases(n, hd))
+        print("mutant lstm (%d, %d) %-38s worst err/bound %.3g" % (n, hd, mutant, worst))
+        assert not worst <= 1.0, mutant
+
+
+@pytest.mark.parametrize("n", C.POSE_NS)
+def test_pose_loss_mutants_are_rejected(n):
+    for mutant in POSE_MUTANTS:
+        worst = 0.0
+        for pred, truth, args in _pose_cases(n):
+            _, grad = pose_loss_f32(pred, truth, *args, mutant=mutant)
+            worst = max(worst, B.check(grad, *B.pose_loss_ref(pred, truth, *args)["grad"], "grad")[1])
+        print("mutant pose n=%d %-30s worst err/bound %.3g" % (n, mutant, worst))
+        assert not worst <= 1.0, mutant
+
+
+@pytest.mark.parametrize("n", C.ADAM_NS)
+def test_adam_mutants_are_rejected(n):
+    for mutant in ADAM_MUTANTS:
+        worst = max(max(_adam_ratios(adam_f32, case, step, mutant=mutant).values()) for case, step in _adam_cases(n))
+        print("mutant adam n=%d %-32s worst err/bound %.3g" % (n, mutant, worst))
+        assert not worst <= 1.0, mutant
+
+
+def test_amp_model_follows_the_protocol():
+    """the Python model of the loss scaler (the GPU test's reference): back-off floored at 1, growth after `interval` finite steps
+    capped at 2^24, skip / streak / steps as amp.py documents them"""
+    st = [4.0, 0.25, 0.0, 0.0, 0.0, 0.0]
+    st = C.amp_model(st, False, 2.0, 0.5, 2)
+    assert st == [4.0, 0.25, 0.0, 0.0, 1.0, 1.0]
+    st = C.amp_model(st, False, 2.0, 0.5, 2)
+    assert st == [8.0, 0.125, 0.0, 0.0, 0.0, 2.0]
+    st = C.amp_model(st, True, 2.0, 0.5, 2)
+    assert st == [4.0, 0.25, 0.0, 1.0, 0.0, 2.0]
+    assert C.amp_model([1.0, 1.0, 0.0, 0.0, 5.0, 7.0], True, 2.0, 0.5, 2) == [1.0, 1.0, 0.0, 1.0, 0.0, 7.0]
+    assert C.amp_model([2.0 ** 24, 2.0 ** -24, 0.0, 0.0, 1.0, 7.0], False, 2.0, 0.5, 2) == [2.0 ** 24, 2.0 ** -24, 0.0, 0.0, 0.0, 8.0]
+    assert C.amp_model([4.0, 0.25, 1.0, 0.0, 1.0, 3.0], False, 2.0, 0.5, 2)[:4] == [2.0, 0.5, 0.0, 1.0]    # found-inf already set

@@ -4,6 +4,7 @@ MFMA, different summation order); bf16 path 2e-2 (8-bit mantissa inputs, fp32 ac
 The GEMM-family kernels are held, besides, to the element-wise bound of tests/_bounds.py (fp32 accumulation + one rounding into
 the output type, against an fp64 reference built on the device from the same operands) and, for 16-bit outputs, to unbiased
 rounding."""
+import ctypes
 import os
 
 import numpy as np
@@ -12,6 +13,7 @@ import torch
 import torch.nn.functional as F
 
 import _bounds as B
+import _scalar_cases as C
 
 pytestmark = pytest.mark.gpu
 
@@ -766,6 +768,232 @@ def test_adam_matches_oracle():
         po.adam_update(p, gstep, m, v, step, lr=1e-3)
         ops.adam_step(pd, gstep.to(DEV), md, vd, 1e-3, 0.9, 0.999, 1e-8, step)
     assert rel_err(pd, p) < 1e-6 and rel_err(md, m) < 1e-6 and rel_err(vd, v) < 1e-6
+
+
+# ------------------------------------------------------------------ the fp32 scalar kernels of csrc/heads.hip, element-wise
+# LSTM cell, pose loss, Adam (both kernels) and the loss scaler, one call at a time against fp64 references built on the host from
+# the same fp32 operands, each element within its propagated bound (tests/_bounds.py: Fx; TR and EW as tests/test_bounds_cpu.py fixed
+# them on these very inputs, tests/_scalar_cases.py).  The second grid-stride trip of the element-wise kernels starts at 2^28 elements
+# (ew_grid caps the grid at 4096 blocks) and stays untested here: nothing of that size is allocated.
+def _P(t):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _S():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _within_all(got, ref, label, layout):
+    """one assert_within over the cases of a shape: got [case](tensor), ref [case](reference, bound) -> stacked, the case index first"""
+    return B.assert_within(torch.stack([g.cpu() for g in got]), torch.stack([r for r, _ in ref]), torch.stack([b for _, b in ref]), label, layout)
+
+
+@pytest.mark.parametrize("n,hd", C.LSTM_SHAPES)
+def test_lstm_cell_elementwise(n, hd):
+    """rpe_lstm_cell_fwd / rpe_lstm_cell_bwd with explicit operands, no GEMM in the loop: the four activated gate blocks written back
+    in place, c, h, the four dgates blocks and dc_io, every element within its bound, for gate pre-activations N(0,1), N(0,1) * 8
+    (sigmoid / tanh tails to |x| ~ 30) and a row at +-90 (exact 0 / 1, finite c and h, zero gate gradients), with and without c_prev.
+    One guard row behind every written tensor stays bitwise as it was."""
+    from rgb_proprioceptive_pose_estimator_amd._lib import lib
+    cases = [(kind, wp) for kind in C.LSTM_KINDS for wp in (False, True)]      # the index c of a failure message
+    names = ("i", "f", "g", "o", "c", "h", "di", "df", "dg", "do", "dc")
+    got, ref = {k: [] for k in names}, {k: [] for k in names}
+    guard = torch.arange(4 * hd, dtype=torch.float32) + 0.5
+    for kind, wp in cases:
+        case = C.lstm_case(n, hd, kind, wp)
+        d = {k: None if v is None else v.to(DEV) for k, v in case.items()}
+        buf = torch.cat([case["gates"], guard[None]]).to(DEV)                  # [n + 1, 4 hd]: the kernel is given n rows
+        c_out, h_out = torch.full((n + 1, hd), 7.0, device=DEV), torch.full((n + 1, hd), 7.0, device=DEV)
+        lib.rpe_lstm_cell_fwd(_P(buf), _P(d["b_ih"]), _P(d["b_hh"]), _P(d["c_prev"]), _P(c_out), _P(h_out), n, hd, _S())
+        act, c, h = buf[:n].cpu(), c_out[:n].cpu(), h_out[:n].cpu()
+        assert torch.equal(buf[n].cpu(), guard), "rpe_lstm_cell_fwd wrote behind gates[N][4 Hd]"
+        assert (c_out[n] == 7.0).all() and (h_out[n] == 7.0).all(), "rpe_lstm_cell_fwd wrote behind c / h"
+        r = B.lstm_cell_fwd_ref(case["gates"], case["b_ih"], case["b_hh"], case["c_prev"])
+        for k, name in enumerate("ifgo"):
+            got[name].append(act[:, k * hd:(k + 1) * hd])
+        got["c"].append(c)
+        got["h"].append(h)
+        # backward from the kernel's own activated gates and c, as the model runs it
+        dc = torch.cat([case["dc_in"], torch.full((1, hd), 7.0)]).to(DEV)
+        dgates = torch.full((n + 1, 4 * hd), 7.0, device=DEV)
+        lib.rpe_lstm_cell_bwd(_P(buf), _P(d["c_prev"]), _P(c_out), _P(d["dh"]), _P(dc), _P(dgates), n, hd, _S())
+        assert (dgates[n] == 7.0).all() and (dc[n] == 7.0).all(), "rpe_lstm_cell_bwd wrote behind dgates / dc_io"
+        assert torch.equal(buf[:n].cpu(), act) and torch.equal(c_out[:n].cpu(), c), "rpe_lstm_cell_bwd changed its inputs"
+        r.update(B.lstm_cell_bwd_ref(act, case["c_prev"], c, case["dh"], case["dc_in"]))
+        dg = dgates[:n].cpu()
+        for k, name in enumerate(("di", "df", "dg", "do")):
+            got[name].append(dg[:, k * hd:(k + 1) * hd])
+        got["dc"].append(dc[:n].cpu())
+        for name in names:
+            ref[name].append(r[name])
+        if kind == "saturated":      # row 0 at +-90: exact 0 / 1 (tanh: +-1), finite c and h, zero gate gradients -- not NaN
+            pre = case["gates"][0]
+            want = torch.where(pre > 0, 1.0, 0.0)
+            want[2 * hd:3 * hd] = torch.sign(pre[2 * hd:3 * hd])
+            assert torch.equal(act[0], want), "saturated gates are not exactly 0 / 1: %s" % (act[0] - want,)
+            assert torch.isfinite(c[0]).all() and torch.isfinite(h[0]).all()
+            assert (dg[0] == 0).all(), "saturated gates have a gradient: %s" % (dg[0],)
+    for name in names:
+        what = "gate %s" % name if name in "ifgo" else ("dgates %s" % name[1] if name in ("di", "df", "dg", "do") else name)
+        _within_all(got[name], ref[name], "lstm_cell %s (%d, %d)" % (what, n, hd), "cnj")
+
+
+def _pose_cases():
+    return [(rot, metric, mode, sa) for rot in C.POSE_ROTS for metric in C.POSE_METRICS for mode in C.POSE_MODES for sa in C.POSE_SCALES]
+
+
+@pytest.mark.parametrize("n", C.POSE_NS)
+def test_pose_loss_elementwise(n):
+    """rpe_pose_loss: the gradient element-wise and the three sums against their bounds, all 4 metrics x 2 modes x 2 (scale, alpha), on
+    seeded rows with the exact rows of _scalar_cases.POSE_EXACT at indices 0, 255, 256 and n - 1 (every exact row at every index over
+    the 5 rotations).  Mode `position`: the quaternion columns are exactly 0.  want_grad=False: the same three sums, bitwise.
+    (The all-zero quaternion is pinned in tests/test_gpu_evaluate.py.)"""
+    cases = _pose_cases()                                                      # the index c of a failure message
+    grads, outs, rg, ro = [], [], [], []
+    for rot, metric, mode, (scale, alpha) in cases:
+        pred, truth = C.pose_rows(n, rot)
+        pd, td = pred.to(DEV), truth.to(DEV)
+        out3, grad = ops.pose_loss(pd, td, metric, mode, scale, alpha, C.POSE_EPS)
+        only, none = ops.pose_loss(pd, td, metric, mode, scale, alpha, C.POSE_EPS, want_grad=False)
+        assert none is None and torch.equal(only.cpu().view(torch.int32), out3.cpu().view(torch.int32)), "the sums depend on want_grad"
+        if mode == 0:
+            assert (grad[:, 3:] == 0).all(), "mode position: a quaternion gradient"
+        r = B.pose_loss_ref(pred, truth, metric, mode, scale, alpha, C.POSE_EPS)
+        grads.append(grad)
+        outs.append(out3)
+        rg.append(r["grad"])
+        ro.append(r["out"])
+    _within_all(grads, rg, "pose_loss grad n=%d" % n, "cik")
+    _within_all(outs, ro, "pose_loss sums n=%d" % n, "ck")
+
+
+@pytest.mark.parametrize("n", C.ADAM_NS)
+def test_adam_elementwise_both_kernels(n):
+    """rpe_adam_step and rpe_adam_step_amp (the kernel FusedAdam launches on the fp16 path and under graph capture: step count and
+    skip flag on the device), p, m and v element-wise at steps 1 .. 100000 from non-zero moments; the two kernels agree to within
+    the sum of both bounds; exact-zero gradients with zero moments leave p bitwise; a set skip flag leaves everything bitwise; slices
+    at element offsets 1, 2, 3 of a larger buffer (arena segments) leave their neighbours bitwise; rpe_adam_step refuses a pointer
+    that is off by 4 bytes and changes nothing."""
+    from rgb_proprioceptive_pose_estimator_amd._lib import lib, raw
+    hp = C.ADAM_HP
+    args = (hp["lr"], hp["b1"], hp["b2"], hp["eps"])
+    cases = [(step, kind) for step in C.ADAM_STEPS for kind in C.ADAM_KINDS]   # the index c of a failure message
+    plain, amp, ref = {k: [] for k in "pmv"}, {k: [] for k in "pmv"}, {k: [] for k in "pmv"}
+
+    def state(step, skip=0.0):
+        return torch.tensor([1.0, 1.0, 0.0, skip, 0.0, float(step), 0.0, 0.0]).to(DEV)
+
+    for step, kind in cases:
+        p, g, m, v = C.adam_case(n, step, kind)
+        r = B.adam_ref(p, g, m, v, step, **hp)
+        pd, gd, md, vd = (t.to(DEV) for t in (p, g, m, v))
+        ops.adam_step(pd, gd, md, vd, *args, step)
+        pa, ga, ma, va = (t.to(DEV) for t in (p, g, m, v))
+        lib.rpe_adam_step_amp(_P(pa), _P(ga), _P(ma), _P(va), n, *args, _P(state(step)), _S())
+        assert torch.equal(gd.cpu(), g) and torch.equal(ga.cpu(), g)
+        for k, a, b in zip("pmv", (pd, md, vd), (pa, ma, va)):
+            plain[k].append(a.cpu())
+            amp[k].append(b.cpu())
+            ref[k].append(r[k])
+        if kind == "zero":           # g = m = v = 0: the update is exactly 0
+            for t in (pd, pa):
+                assert torch.equal(t.cpu().view(torch.int32), p.view(torch.int32)), "a zero update changed p"
+            assert not md.any() and not vd.any() and not ma.any() and not va.any()
+    for k in "pmv":
+        _within_all(plain[k], ref[k], "adam_step %s n=%d" % (k, n), "ci")
+        _within_all(amp[k], ref[k], "adam_step_amp %s n=%d" % (k, n), "ci")
+        both = [(a.double(), 2.0 * b) for a, (_, b) in zip(plain[k], ref[k])]      # two kernels with one rule: the sum of both bounds
+        _within_all(amp[k], both, "adam_step_amp vs adam_step %s n=%d" % (k, n), "ci")
+    # skip flag set: nothing moves
+    step = 10
+    p, g, m, v = C.adam_case(n, step, "unit")
+    pa, ga, ma, va = (t.to(DEV) for t in (p, g, m, v))
+    lib.rpe_adam_step_amp(_P(pa), _P(ga), _P(ma), _P(va), n, *args, _P(state(step, skip=1.0)), _S())
+    for t, t0 in ((pa, p), (ga, g), (ma, m), (va, v)):
+        assert torch.equal(t.cpu(), t0), "rpe_adam_step_amp moved a buffer although skip is set"
+    # slices of a larger buffer, as arena segments may start anywhere
+    P8, G8, M8, V8 = C.adam_case(n + 8, step, "unit")
+    for off in (1, 2, 3):
+        big = [t.to(DEV) for t in (P8, G8, M8, V8)]
+        sl = [t[off:off + n] for t in big]
+        lib.rpe_adam_step_amp(_P(sl[0]), _P(sl[1]), _P(sl[2]), _P(sl[3]), n, *args, _P(state(step)), _S())
+        r = B.adam_ref(*(t[off:off + n] for t in (P8, G8, M8, V8)), step, **hp)
+        for k, t, t0 in zip("pmv", (big[0], big[2], big[3]), (P8, M8, V8)):
+            B.assert_within(t[off:off + n], *r[k], "adam_step_amp %s n=%d at offset %d" % (k, n, off), "i")
+            assert torch.equal(t[:off].cpu(), t0[:off]) and torch.equal(t[off + n:].cpu(), t0[off + n:]), "a neighbour of the slice moved"
+        assert torch.equal(big[1].cpu(), G8)
+    # rpe_adam_step needs 16-byte aligned buffers: one pointer off by 4 bytes -> RPE_ERR_ALIGN, nothing written
+    big = [t.to(DEV) for t in (P8, G8, M8, V8)]
+    for bad in range(4):
+        ptrs = [ctypes.c_void_p(t.data_ptr() + (4 if i == bad else 0)) for i, t in enumerate(big)]
+        rc = raw.rpe_adam_step(*ptrs, n, *args, step, _S())
+        assert rc == 3, "rpe_adam_step took a misaligned pointer (status %d)" % rc
+    torch.cuda.synchronize()
+    for t, t0 in zip(big, (P8, G8, M8, V8)):
+        assert torch.equal(t.cpu(), t0), "rpe_adam_step wrote although it returned the alignment error"
+
+
+@pytest.mark.parametrize("n", C.AMP_NS)
+def test_loss_scaler_state_machine(n):
+    """rpe_amp_unscale + rpe_amp_update against the Python model of the protocol documented in amp.py (_scalar_cases.amp_model): one
+    inf / -inf / NaN at every position class (element 0, the 4-wide body, the last full vector, each tail element, another block)
+    sets found-inf, backs the scale off (floored at 1), refreshes 1 / scale, sets skip, zeroes the streak, leaves `steps` and clears
+    found-inf; the largest finite value does not trip it; finite gradients are unscaled exactly (a power of two), the streak counts
+    to `interval`, then the scale grows (capped at 2^24) and `steps` increments.  (A value that overflows only through 1 / scale
+    cannot occur: scale >= 1 always.)"""
+    from rgb_proprioceptive_pose_estimator_amd._lib import lib
+    growth, backoff, interval = 2.0, 0.5, 2
+    g0 = torch.randn(n, generator=torch.Generator().manual_seed(n)) * 64.0
+
+    def run(g, st6):
+        gd, st = g.to(DEV), torch.tensor(list(st6) + [0.0, 0.0]).to(DEV)
+        lib.rpe_amp_unscale(_P(gd), n, _P(st), _S())
+        mid = st.cpu()
+        lib.rpe_amp_update(_P(st), growth, backoff, interval, _S())
+        return gd.cpu(), mid, st.cpu()
+
+    def unscaled_ok(got, g, inv):
+        want = g * torch.tensor(inv, dtype=torch.float32)                      # by a power of two: exact
+        fin = torch.isfinite(want)
+        return torch.equal(got[fin].view(torch.int32), want[fin].view(torch.int32)) and not torch.isfinite(got[~fin]).any()
+
+    st0 = [4096.0, 1.0 / 4096.0, 0.0, 0.0, 1.0, 7.0]
+    for where, i in C.amp_positions(n).items():
+        for bad in C.AMP_BAD:
+            g = g0.clone()
+            g[i] = bad
+            got, mid, st = run(g, st0)
+            tag = "%r at %s (element %d of %d)" % (bad, where, i, n)
+            assert mid[2].item() == 1.0 and mid.tolist()[:2] == st0[:2] and mid.tolist()[3:] == st0[3:] + [0.0, 0.0], "unscale, %s: %s" % (tag, mid.tolist())
+            assert st.tolist() == [2048.0, 1.0 / 2048.0, 0.0, 1.0, 0.0, 7.0, 0.0, 0.0], "update, %s: %s" % (tag, st.tolist())
+            assert st.tolist()[:6] == C.amp_model(st0, True, growth, backoff, interval)
+            assert unscaled_ok(got, g, st0[1]), tag
+    g = g0.clone()
+    g[n - 1] = float("inf")
+    _, _, st = run(g, [1.0, 1.0, 0.0, 0.0, 3.0, 7.0])                           # the back-off is floored at 1
+    assert st.tolist()[:6] == [1.0, 1.0, 0.0, 1.0, 0.0, 7.0]
+    for scale in (1.0, 4096.0):                                                # the largest finite value is finite
+        g = g0.clone()
+        g[0], g[n - 1] = C.FLT_MAX, -C.FLT_MAX
+        s0 = [scale, 1.0 / scale, 0.0, 0.0, 0.0, 7.0]
+        got, mid, st = run(g, s0)
+        assert mid[2].item() == 0.0, "the largest finite fp32 value tripped found-inf at scale %g" % scale
+        assert st.tolist()[:6] == C.amp_model(s0, False, growth, backoff, interval) == [scale, 1.0 / scale, 0.0, 0.0, 1.0, 8.0]
+        assert unscaled_ok(got, g, s0[1])
+    _, _, st = run(g0, [2.0 ** 24, 2.0 ** -24, 0.0, 0.0, 1.0, 7.0])            # growth is capped at 2^24
+    assert st.tolist()[:6] == [2.0 ** 24, 2.0 ** -24, 0.0, 0.0, 0.0, 8.0]
+    # six steps with interval 2: finite, finite (grows), inf (backs off), finite, NaN, finite -- the whole state after every step
+    st6 = [4096.0, 1.0 / 4096.0, 0.0, 0.0, 0.0, 0.0]
+    for k, bad in enumerate((None, None, float("inf"), None, float("nan"), None)):
+        g = g0.clone()
+        if bad is not None:
+            g[(k * 7919) % n] = bad
+        got, _, st = run(g, st6)
+        want = C.amp_model(st6, bad is not None, growth, backoff, interval)
+        assert st.tolist()[:6] == want, "step %d: state %s, model %s" % (k, st.tolist()[:6], want)
+        assert unscaled_ok(got, g, st6[1])
+        st6 = want
+    assert st6 == [2048.0, 1.0 / 2048.0, 0.0, 0.0, 1.0, 4.0]
 
 
 def test_small_utils():
