@@ -449,6 +449,25 @@ int rpe_amp_update(float* state, float growth_factor, float backoff_factor, int 
 int rpe_adam_step_amp(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2, double eps, const float* state,
                       void* stream);
 
+/* replaces: torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm) followed by torch.optim.AdamW(..., weight_decay).step()
+ * (neither is in the reference, which trains with plain Adam: scripts/train_model.py:228), over the flat gradient arena and
+ * without a host round trip.
+ * grad_sumsq: sum of squares of one gradient segment g[0..n), every element widened to fp64 BEFORE it is squared (1e20 does not
+ *     overflow, 1e-20 does not underflow), as rpe_grad_sumsq_rows(n) fp64 partial rows written with plain stores to `partials`
+ *     (the caller passes its own row offset per segment).  The row count is a function of n alone -- never of the device -- so
+ *     data-parallel ranks sum in the same order.  n >= 1; g must be 16-byte aligned.
+ * clip_coef: one workgroup sums `rows` partials in a fixed order in fp64 and writes state[6] = (float)sqrt(sum), state[7] =
+ *     (float)min(1, max_norm / (norm + 1e-6)) -- torch's rule, evaluated in fp64 and rounded once.  max_norm <= 0 or +inf:
+ *     measure only, coefficient 1.  rows == 0: norm 0, coefficient 1.  A NaN norm gives a NaN coefficient, an infinite norm 0.
+ * adamw_step_clip: rpe_adam_step_amp (step count state[5], skip flag state[3]) with gc = g * state[7] when use_clip is set,
+ *     m' = m + (gc - m)(1 - beta1), v' = v beta2 + gc gc (1 - beta2), p' = p (1 - lr weight_decay) - (lr / bc1) m' / (sqrt(v') /
+ *     sqrt(bc2) + eps): decoupled decay applied to the old p.  g is NOT written (torch's clip scales .grad in place). */
+long rpe_grad_sumsq_rows(long n);
+int rpe_grad_sumsq(const float* g, long n, double* partials, void* stream);
+int rpe_clip_coef(const double* partials, long rows, double max_norm, float* state, void* stream);
+int rpe_adamw_step_clip(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, const float* state, int use_clip, void* stream);
+
 /* ------------------------------------------------------------------ ResNet-50 trunk engine */
 /* One object = one (batch, dtype) plan for the whole torchvision-shaped ResNet-50 body:
  * stage image -> conv1/bn1/relu -> maxpool -> 16 bottlenecks -> avgpool -> fc, forward and

@@ -132,6 +132,10 @@ _SPEC = {
     "rpe_amp_unscale": (I, [P, L, P, P]),
     "rpe_amp_update": (I, [P, F, F, I, P]),
     "rpe_adam_step_amp": (I, [P, P, P, P, L, D, D, D, D, P, P]),
+    "rpe_grad_sumsq_rows": (L, [L]),
+    "rpe_grad_sumsq": (I, [P, L, P, P]),
+    "rpe_clip_coef": (I, [P, L, D, P, P]),
+    "rpe_adamw_step_clip": (I, [P, P, P, P, L, D, D, D, D, D, P, I, P]),
     "rpe_resnet50_create": (I, [POINTER(c_void_p), I, I, I, I, I]),
     "rpe_resnet_create": (I, [POINTER(c_void_p), I, I, I, I, I, I]),
     "rpe_resnet50_destroy": (None, [P]),
@@ -175,7 +179,7 @@ _SPEC = {
     "rpe_feature_mosaic": (I, [P, P, I, I, I, I, I, I, P, P]),
 }
 # entry points whose int return value is data, not a status
-_NOT_STATUS = {"rpe_abi_version", "rpe_conv2d_wgrad_halo_min_width"}
+_NOT_STATUS = {"rpe_abi_version", "rpe_conv2d_wgrad_halo_min_width", "rpe_grad_sumsq_rows"}
 
 EXPORTS = tuple(_SPEC)
 

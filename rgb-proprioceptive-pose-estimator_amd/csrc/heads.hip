@@ -677,6 +677,92 @@ __global__ __launch_bounds__(256) void adam_amp_kernel(float* __restrict__ p, co
 }
 
 // ---------------------------------------------------------------------------------------------
+// Global gradient-norm clipping + decoupled weight decay (torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW over the arena).
+// st[6] gradient norm and st[7] clip coefficient join the state block above.  Three launches, nothing read by the host:
+//   grad_sumsq_kernel   per segment: fp64 sum of squares as one partial row per block (plain stores, no atomics, no fences: the
+//                       launch boundary publishes the rows).  The grid is a function of n alone (grad_sumsq_rows), so two
+//                       data-parallel ranks, whatever their devices, add the same numbers in the same order.
+//   clip_coef_kernel    one workgroup adds the rows in a fixed order and writes norm and coefficient.
+//   adamw_clip_kernel   the update; g is read, never written.
+// ---------------------------------------------------------------------------------------------
+constexpr long kSumsqMaxRows = 1024;      // blocks (= partial rows) per segment at most
+constexpr long kSumsqBlockElems = 1024;   // elements one block takes per grid-stride trip: 256 threads x one 16-byte load
+
+static inline long grad_sumsq_rows(long n) {
+    long r = (n + kSumsqBlockElems - 1) / kSumsqBlockElems;
+    return r < 1 ? 1 : (r > kSumsqMaxRows ? kSumsqMaxRows : r);
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const float* __restrict__ g, long n, double* __restrict__ part) {
+    __shared__ double red[4];
+    const long n4 = n >> 2;
+    double acc = 0.0;
+#pragma unroll 4
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const f32x4 gg = ((const f32x4*)g)[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double x = (double)gg[k];   // widened BEFORE the square: 1e20 does not overflow, 1e-20 does not underflow
+            acc += x * x;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const double x = (double)g[(n4 << 2) + threadIdx.x];
+        acc += x * x;
+    }
+    acc = block_sum_d(acc, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = acc;
+}
+
+__global__ __launch_bounds__(256) void clip_coef_kernel(const double* __restrict__ part, long rows, double max_norm, float* __restrict__ st) {
+    __shared__ double red[4];
+    double acc = 0.0;
+    for (long i = threadIdx.x; i < rows; i += 256) acc += part[i];
+    const double norm = sqrt(block_sum_d(acc, red));
+    if (threadIdx.x != 0) return;
+    double coef = 1.0;
+    if (max_norm > 0.0 && max_norm <= 1.7976931348623157e308) {   // else (<= 0, +inf, NaN): measure only
+        const double c = max_norm / (norm + 1e-6);
+        coef = (c > 1.0) ? 1.0 : c;   // not fmin: a NaN norm stays a NaN coefficient (torch, error_if_nonfinite=False); inf -> 0
+    }
+    st[6] = (float)norm;
+    st[7] = (float)coef;
+}
+
+// adam_amp_kernel's device-side step count and skip flag, adam_kernel's 4-wide body; decay = 1 - lr weight_decay multiplies the
+// OLD p (torch.optim.AdamW's order), coef = st[7] scales the gradient on its way into both moments
+__global__ __launch_bounds__(256) void adamw_clip_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                        long n, float lr, double b1, double b2, float eps, float decay, const float* __restrict__ st,
+                                                        int use_clip) {
+    if (st[3] != 0.f) return;   // non-finite gradients this step: parameters and moments stay as they are
+    const double step = (double)st[5];
+    const float bc1 = (float)(1.0 - pow(b1, step)), bc2_sqrt = (float)sqrt(1.0 - pow(b2, step));
+    const float omb1 = (float)(1.0 - b1), omb2 = (float)(1.0 - b2), fb2 = (float)b2;
+    const float coef = use_clip ? st[7] : 1.f;   // (g * 1.f is g)
+    const long n4 = n >> 2;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        f32x4 pp = ((f32x4*)p)[i], gg = ((const f32x4*)g)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float gc = gg[k] * coef;
+            mm[k] = mm[k] + (gc - mm[k]) * omb1;
+            vv[k] = vv[k] * fb2 + gc * gc * omb2;
+            const float denom = sqrtf(vv[k]) / bc2_sqrt + eps;
+            pp[k] = pp[k] * decay - (lr / bc1) * (mm[k] / denom);
+        }
+        ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = (n4 << 2) + threadIdx.x;
+        const float gc = g[i] * coef;
+        const float mi = m[i] + (gc - m[i]) * omb1;
+        const float vi = v[i] * fb2 + gc * gc * omb2;
+        m[i] = mi; v[i] = vi;
+        p[i] = p[i] * decay - (lr / bc1) * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // weight packing / small utilities
 // ---------------------------------------------------------------------------------------------
 // w: [Co][R][S][Ci] fp32 (channels_last storage of an OIHW parameter)
@@ -1054,6 +1140,34 @@ int rpe_adam_step_amp(float* p, const float* g, float* m, float* v, long n, doub
     if (n <= 0) return 0;
     if (!state) return rpe_set_error(RPE_ERR_SHAPE, "adam_step_amp: null state");
     hipLaunchKernelGGL(adam_amp_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)lr, beta1, beta2, (float)eps, state);
+    RPE_CHECK_LAUNCH();
+    return 0;
+}
+
+long rpe_grad_sumsq_rows(long n) { return grad_sumsq_rows(n); }
+
+int rpe_grad_sumsq(const float* g, long n, double* partials, void* stream) {
+    if (n <= 0 || !g || !partials) return rpe_set_error(RPE_ERR_SHAPE, "grad_sumsq: n >= 1, g and partials are required");
+    if ((((uintptr_t)g) & 15) || (((uintptr_t)partials) & 7)) return rpe_set_error(RPE_ERR_ALIGN, "grad_sumsq: g must be 16-byte aligned, partials 8-byte");
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)grad_sumsq_rows(n)), dim3(256), 0, (hipStream_t)stream, g, n, partials);
+    RPE_CHECK_LAUNCH();
+    return 0;
+}
+
+int rpe_clip_coef(const double* partials, long rows, double max_norm, float* state, void* stream) {
+    if (!state || rows < 0 || (rows > 0 && !partials)) return rpe_set_error(RPE_ERR_SHAPE, "clip_coef: bad arguments");
+    hipLaunchKernelGGL(clip_coef_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, partials, rows, max_norm, state);
+    RPE_CHECK_LAUNCH();
+    return 0;
+}
+
+int rpe_adamw_step_clip(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2, double eps,
+                        double weight_decay, const float* state, int use_clip, void* stream) {
+    if (n <= 0) return 0;
+    if (!state) return rpe_set_error(RPE_ERR_SHAPE, "adamw_step_clip: null state");
+    if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return rpe_set_error(RPE_ERR_ALIGN, "adamw_step_clip: buffers must be 16-byte aligned");
+    hipLaunchKernelGGL(adamw_clip_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)lr, beta1, beta2, (float)eps,
+                       (float)(1.0 - lr * weight_decay), state, use_clip);
     RPE_CHECK_LAUNCH();
     return 0;
 }

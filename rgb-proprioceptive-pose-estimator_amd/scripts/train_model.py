@@ -5,7 +5,7 @@ Keeps every flag of the reference's scripts/train_model.py:17-47 (names, types, 
 dispatch (:158-218), criterion dict (:100-105), Adam (:228) and train() call (:248-259).  The Robosuite environment
 the reference builds at import time (:84-97) is replaced by seeded synthetic Robosuite-shaped episodes; flags that only
 configure the simulator (--controller, --robots, --use_placement_initializer, --motion) are accepted and recorded.
-Added flags: --dtype {bf16,f16,f32}, --optimizer {fused,torch}, --episodes_seed.
+Added flags: --dtype {bf16,f16,f32}, --optimizer {fused,torch}, --max_grad_norm, --weight_decay, --episodes_seed.
 
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 scripts/train_model.py ...`;
 episodes are sharded over ranks and gradients SUM-all-reduced over RCCL.
@@ -58,6 +58,9 @@ def build_parser():
     p.add_argument("--dtype", choices=["bf16", "f16", "f32"], default="bf16",
                    help="compute dtype of the conv trunk (fp32 accumulate either way; f16 adds dynamic loss scaling and needs --optimizer fused)")
     p.add_argument("--optimizer", choices=["fused", "torch"], default="fused", help="FusedAdam (one HIP kernel) or torch.optim.Adam")
+    p.add_argument("--max_grad_norm", type=float, default=None,
+                   help="clip the global gradient norm to this value on the device before the Adam update (default: off; needs --optimizer fused)")
+    p.add_argument("--weight_decay", type=float, default=0.0, help="decoupled weight decay (AdamW; default 0 = plain Adam)")
     p.add_argument("--episodes_seed", type=int, default=1234, help="seed of the synthetic episode generator")
     p.add_argument("--no_save", action="store_true", help="do not write the best-validation checkpoint")
     p.add_argument("--episodes", type=str, default=None, metavar="FILE.npz",
@@ -94,11 +97,26 @@ def build_model(args, compute_dtype):
                                                        proprio_hidden_dim=args.proprio_hidden_dim, **common)
 
 
+def build_optimizer(args, params):
+    """--optimizer / --max_grad_norm / --weight_decay -> FusedAdam, FusedAdamW, torch.optim.Adam or torch.optim.AdamW"""
+    from rgb_proprioceptive_pose_estimator_amd.optim import FusedAdam, FusedAdamW
+    if args.dtype == "f16" and args.optimizer != "fused":
+        raise SystemExit("--dtype f16 needs --optimizer fused: the loss-scale unscale / skip logic lives in FusedAdam.step (amp.py)")
+    if args.max_grad_norm is not None and args.optimizer != "fused":
+        raise SystemExit("--max_grad_norm needs --optimizer fused: the on-device norm and clip live in FusedAdam.step (optim.py)")
+    if args.optimizer == "fused":
+        if args.weight_decay:
+            return FusedAdamW(params, lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm)
+        return FusedAdam(params, lr=args.lr, max_grad_norm=args.max_grad_norm)
+    if args.weight_decay:
+        return torch.optim.AdamW(params, lr=args.lr, weight_decay=args.weight_decay)
+    return torch.optim.Adam(params, lr=args.lr)
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     from rgb_proprioceptive_pose_estimator_amd.dist import init_from_env
     from rgb_proprioceptive_pose_estimator_amd.models import PoseDistanceLoss
-    from rgb_proprioceptive_pose_estimator_amd.optim import FusedAdam
     from rgb_proprioceptive_pose_estimator_amd.util.data_utils import RecordedEpisodeDataset, SyntheticEpisodeDataset
     from rgb_proprioceptive_pose_estimator_amd.util.learn_utils import train
 
@@ -120,10 +138,7 @@ def main(argv=None):
     model = build_model(args, DTYPES[args.dtype])
     if args.load_checkpoint:
         model.load_state_dict(torch.load(args.checkpoint_model_path, map_location="cpu"))
-    if args.dtype == "f16" and args.optimizer != "fused":
-        raise SystemExit("--dtype f16 needs --optimizer fused: the loss-scale unscale / skip logic lives in FusedAdam.step (amp.py)")
-    opt_cls = FusedAdam if args.optimizer == "fused" else torch.optim.Adam
-    optimizer = opt_cls(model.parameters(), lr=args.lr)
+    optimizer = build_optimizer(args, model.parameters())
     if args.episodes:
         dataset = RecordedEpisodeDataset(args.episodes, use_depth=args.use_depth, obj_name=args.obj_name, seed=args.episodes_seed + 1000 * rank)
         if args.horizon != build_parser().get_default("horizon") and args.horizon != dataset.env.horizon and rank == 0:

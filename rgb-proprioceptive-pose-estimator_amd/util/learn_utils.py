@@ -415,6 +415,9 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
             dataset.refresh_data(hi - lo, params["camera_name"], params["noise_scale"])
             model.reset_initial_state(hi - lo)
             sums = torch.zeros(3, dtype=torch.float64, device="cuda")
+            # gradient clipping on (FusedAdam(max_grad_norm=...)): the norm of every step and the count of clipped ones, on the device
+            clip_sums = torch.zeros(2, dtype=torch.float64, device="cuda") if phase == "train" and getattr(optimizer, "max_grad_norm", None) is not None else None
+            clip_steps = 0
             horizon = len(dataset)
             for img, depth, x0bar, x0, x1, obj in _chunks(dataset, horizon, seq, model.use_depth if hasattr(model, "use_depth") else False):
                 if not model.requires_sequence:  # the reference squeezes the leading batch-of-1 dim (learn_utils.py:141-149)
@@ -424,9 +427,12 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
                     obj = None if obj is None else obj[0]
                 loss, pe, oe = train_step(model, (img, depth, x0bar, x0, x1, obj), criterion, optimizer, train_obj_pose, phase, grad_sync)
                 sums += torch.stack([loss.double(), pe.double(), oe.double()])
+                if clip_sums is not None:
+                    clip_sums += torch.stack([optimizer.grad_norm.double(), (optimizer.clip_coef < 1.0).double()])
+                    clip_steps += 1
             if world > 1:
                 dist.all_reduce(sums)
-            tot = sums.tolist()  # the one host synchronisation of the phase
+            tot = (sums if clip_sums is None else torch.cat([sums, clip_sums])).tolist()  # the one host synchronisation of the phase
             denom = horizon * num_episodes
             epoch_loss, epoch_pos_err, epoch_ori_err = tot[0] / denom, tot[1] / denom, tot[2] / denom
             time_elapsed = time.time() - since
@@ -435,6 +441,9 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
                 writer.add_scalar("Loss/" + tag, epoch_loss, epoch)
                 writer.add_scalar("Err_pos/" + tag, epoch_pos_err, epoch)
                 writer.add_scalar("Err_ori/" + tag, epoch_ori_err, epoch)
+                if clip_sums is not None and clip_steps:   # every rank clips the same reduced gradient: rank 0's figures are everyone's
+                    writer.add_scalar("GradNorm/" + tag, tot[3] / clip_steps, epoch)
+                    writer.add_scalar("GradClipped/" + tag, tot[4] / clip_steps, epoch)
             if logging and rank == 0:
                 print('{} Loss: {:.4f}, PosErr: {:.4f}, OriErr: {:.4f}. Time elapsed = {:.0f}m {:.0f}s'.format(
                     phase, epoch_loss, epoch_pos_err, epoch_ori_err, time_elapsed // 60, time_elapsed % 60))
