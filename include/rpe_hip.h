@@ -468,6 +468,28 @@ int rpe_clip_coef(const double* partials, long rows, double max_norm, float* sta
 int rpe_adamw_step_clip(float* p, const float* g, float* m, float* v, long n, double lr, double beta1, double beta2, double eps,
                         double weight_decay, const float* state, int use_clip, void* stream);
 
+/* replaces: a torch.optim.lr_scheduler stepped on the host (LinearLR warm-up followed by CosineAnnealingLR / StepLR / nothing) and
+ * torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(decay)); neither is in the reference, which builds a plain
+ * Adam with no schedule (scripts/train_model.py:228).  Both live on the device, so a captured train step advances them at every replay.
+ * lr_schedule: one small launch after the step bump.  e = (long)state[5] - 1, the optimizer steps taken before this one; the factor
+ *     f(e) is evaluated in fp64 and rounded once:  e < warmup_steps: s + (1 - s) e / W (s = warmup_start_factor);  kind 0 (constant):
+ *     1;  kind 1 (cosine): fmin + (1 - fmin)(1 + cos(pi (min(e, T) - W) / (T - W))) / 2, held at fmin beyond T = total_steps;  kind 2
+ *     (step): gamma^((e - W) / step_size), the quotient floored.  sched[0] = f, sched[1] = (float)e; `sched` is a block of 4 floats of
+ *     its own, and `state` is read, never written.  state[3] != 0 (a skipped fp16 step): sched stays as it was.  The count is a float:
+ *     exact up to 2^24 steps.  Refused (nothing launched): warmup_steps < 0, cosine with total_steps <= warmup_steps, step_size < 1,
+ *     warmup_start_factor or min_factor outside [0, 1], gamma outside (0, 1], an unknown kind, null pointers.
+ * adamw_step_sched: rpe_adamw_step_clip at the rate lr (double)sched[0]: rate and decay factor 1 - lr_eff weight_decay are formed in
+ *     double and rounded once each, so sched[0] == 1 and ema == NULL give rpe_adamw_step_clip's bits.  ema != NULL: ema' = ema + (p' -
+ *     ema)(1 - ema_decay) from the NEW p' (ema_decay in [0, 1)).  A set skip flag leaves p, m, v and ema as they are; g is never
+ *     written.  All five buffers must be 16-byte aligned.
+ * swap_f32: exchanges a[0..n) and b[0..n) in place (the averaged weights into the arena and back, without an arena-sized
+ *     temporary).  16-byte aligned, not overlapping. */
+int rpe_lr_schedule(const float* state, int kind, long warmup_steps, double warmup_start_factor, long total_steps, double min_factor,
+                    long step_size, double gamma, float* sched, void* stream);
+int rpe_adamw_step_sched(float* p, const float* g, float* m, float* v, float* ema, long n, double lr, double beta1, double beta2, double eps,
+                         double weight_decay, double ema_decay, const float* state, const float* sched, int use_clip, void* stream);
+int rpe_swap_f32(float* a, float* b, long n, void* stream);
+
 /* ------------------------------------------------------------------ ResNet-50 trunk engine */
 /* One object = one (batch, dtype) plan for the whole torchvision-shaped ResNet-50 body:
  * stage image -> conv1/bn1/relu -> maxpool -> 16 bottlenecks -> avgpool -> fc, forward and

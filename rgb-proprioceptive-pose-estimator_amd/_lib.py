@@ -136,6 +136,9 @@ _SPEC = {
     "rpe_grad_sumsq": (I, [P, L, P, P]),
     "rpe_clip_coef": (I, [P, L, D, P, P]),
     "rpe_adamw_step_clip": (I, [P, P, P, P, L, D, D, D, D, D, P, I, P]),
+    "rpe_lr_schedule": (I, [P, I, L, D, L, D, L, D, P, P]),
+    "rpe_adamw_step_sched": (I, [P, P, P, P, P, L, D, D, D, D, D, D, P, P, I, P]),
+    "rpe_swap_f32": (I, [P, P, L, P]),
     "rpe_resnet50_create": (I, [POINTER(c_void_p), I, I, I, I, I]),
     "rpe_resnet_create": (I, [POINTER(c_void_p), I, I, I, I, I, I]),
     "rpe_resnet50_destroy": (None, [P]),

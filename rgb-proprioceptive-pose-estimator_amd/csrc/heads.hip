@@ -763,6 +763,101 @@ __global__ __launch_bounds__(256) void adamw_clip_kernel(float* __restrict__ p, 
 }
 
 // ---------------------------------------------------------------------------------------------
+// Learning-rate schedule on the device + weight EMA fused into the update.  sched: 4 floats of its own, sched[0] the factor that
+// multiplies lr, sched[1] the optimizer steps taken before this one; the 8-float state block is read, never written.
+//   lr_schedule_kernel  one thread, after the step bump: e = st[5] - 1, f(e) in fp64, rounded once.  A skipped fp16 step leaves
+//                       sched as it was (st[5] did not advance either).
+//   adamw_sched_kernel  adamw_clip_kernel with lr_eff = lr sched[0], and ema' = ema + (p' - ema)(1 - ema_decay) from the register
+//                       that holds the new p.
+//   swap_f32_kernel     in-place exchange of two buffers (the average into the arena and back).
+// ---------------------------------------------------------------------------------------------
+enum { kSchedConstant = 0, kSchedCosine = 1, kSchedStep = 2 };
+
+__global__ void lr_schedule_kernel(const float* __restrict__ st, int kind, long W, double s, long T, double fmin, long step_size, double gamma,
+                                   float* __restrict__ sched) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    if (st[3] != 0.f) return;   // a skipped step does not advance the schedule
+    long e = (long)st[5] - 1;
+    if (e < 0) e = 0;
+    double f = 1.0;
+    if (e < W) {
+        f = s + (1.0 - s) * (double)e / (double)W;
+    } else if (kind == kSchedCosine) {
+        const long ec = e < T ? e : T;   // beyond T: hold fmin
+        f = fmin + (1.0 - fmin) * (1.0 + cos(3.141592653589793 * (double)(ec - W) / (double)(T - W))) / 2.0;
+    } else if (kind == kSchedStep) {
+        f = pow(gamma, (double)((e - W) / step_size));
+    }
+    sched[0] = (float)f;
+    sched[1] = (float)e;
+}
+
+// the two scalars rpe_adamw_step_clip forms on the host, formed here from lr sched[0]: product and difference rounded separately (no
+// fused multiply-add), so that a factor of exactly 1 gives the host's bits
+__device__ inline void sched_rate(double lr, double wd, float factor, float* lr_eff, float* decay) {
+#pragma clang fp contract(off)
+    const double r = lr * (double)factor;
+    const double prod = r * wd;
+    *lr_eff = (float)r;
+    *decay = (float)(1.0 - prod);
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw_sched_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                                         float* __restrict__ ema, long n, double lr_base, double b1, double b2, float eps, double wd,
+                                                         float omd, const float* __restrict__ st, const float* __restrict__ sched, int use_clip) {
+    if (st[3] != 0.f) return;   // non-finite gradients this step: parameters, moments and average stay as they are
+    const double step = (double)st[5];
+    const float bc1 = (float)(1.0 - pow(b1, step)), bc2_sqrt = (float)sqrt(1.0 - pow(b2, step));
+    const float omb1 = (float)(1.0 - b1), omb2 = (float)(1.0 - b2), fb2 = (float)b2;
+    const float coef = use_clip ? st[7] : 1.f;   // (g * 1.f is g)
+    float lr, decay;
+    sched_rate(lr_base, wd, sched[0], &lr, &decay);
+    const long n4 = n >> 2;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        f32x4 pp = ((f32x4*)p)[i], gg = ((const f32x4*)g)[i], mm = ((f32x4*)m)[i], vv = ((f32x4*)v)[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float gc = gg[k] * coef;
+            mm[k] = mm[k] + (gc - mm[k]) * omb1;
+            vv[k] = vv[k] * fb2 + gc * gc * omb2;
+            const float denom = sqrtf(vv[k]) / bc2_sqrt + eps;
+            pp[k] = pp[k] * decay - (lr / bc1) * (mm[k] / denom);
+        }
+        ((f32x4*)p)[i] = pp; ((f32x4*)m)[i] = mm; ((f32x4*)v)[i] = vv;
+        if (EMA) {
+            f32x4 ee = ((f32x4*)ema)[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) ee[k] = ee[k] + (pp[k] - ee[k]) * omd;
+            ((f32x4*)ema)[i] = ee;
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = (n4 << 2) + threadIdx.x;
+        const float gc = g[i] * coef;
+        const float mi = m[i] + (gc - m[i]) * omb1;
+        const float vi = v[i] * fb2 + gc * gc * omb2;
+        m[i] = mi; v[i] = vi;
+        const float pi = p[i] * decay - (lr / bc1) * (mi / (sqrtf(vi) / bc2_sqrt + eps));
+        p[i] = pi;
+        if (EMA) ema[i] = ema[i] + (pi - ema[i]) * omd;
+    }
+}
+
+__global__ __launch_bounds__(256) void swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, long n) {
+    const long n4 = n >> 2;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const f32x4 x = ((f32x4*)a)[i], y = ((f32x4*)b)[i];
+        ((f32x4*)a)[i] = y; ((f32x4*)b)[i] = x;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = (n4 << 2) + threadIdx.x;
+        const float x = a[i], y = b[i];
+        a[i] = y; b[i] = x;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // weight packing / small utilities
 // ---------------------------------------------------------------------------------------------
 // w: [Co][R][S][Ci] fp32 (channels_last storage of an OIHW parameter)
@@ -1168,6 +1263,50 @@ int rpe_adamw_step_clip(float* p, const float* g, float* m, float* v, long n, do
     if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v)) & 15) return rpe_set_error(RPE_ERR_ALIGN, "adamw_step_clip: buffers must be 16-byte aligned");
     hipLaunchKernelGGL(adamw_clip_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n, (float)lr, beta1, beta2, (float)eps,
                        (float)(1.0 - lr * weight_decay), state, use_clip);
+    RPE_CHECK_LAUNCH();
+    return 0;
+}
+
+int rpe_lr_schedule(const float* state, int kind, long warmup_steps, double warmup_start_factor, long total_steps, double min_factor,
+                    long step_size, double gamma, float* sched, void* stream) {
+    if (!state || !sched) return rpe_set_error(RPE_ERR_SHAPE, "lr_schedule: null state or sched");
+    if (kind != kSchedConstant && kind != kSchedCosine && kind != kSchedStep) return rpe_set_error(RPE_ERR_SHAPE, "lr_schedule: kind must be 0 (constant), 1 (cosine) or 2 (step)");
+    if (warmup_steps < 0) return rpe_set_error(RPE_ERR_SHAPE, "lr_schedule: warmup_steps >= 0");
+    if (!(warmup_start_factor >= 0.0 && warmup_start_factor <= 1.0)) return rpe_set_error(RPE_ERR_SHAPE, "lr_schedule: warmup_start_factor in [0, 1]");
+    if (!(min_factor >= 0.0 && min_factor <= 1.0)) return rpe_set_error(RPE_ERR_SHAPE, "lr_schedule: min_factor in [0, 1]");
+    if (kind == kSchedCosine && total_steps <= warmup_steps) return rpe_set_error(RPE_ERR_SHAPE, "lr_schedule: cosine needs total_steps > warmup_steps");
+    if (step_size < 1) return rpe_set_error(RPE_ERR_SHAPE, "lr_schedule: step_size >= 1");
+    if (!(gamma > 0.0 && gamma <= 1.0)) return rpe_set_error(RPE_ERR_SHAPE, "lr_schedule: gamma in (0, 1]");
+    hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, kind, warmup_steps, warmup_start_factor, total_steps,
+                       min_factor, step_size, gamma, sched);
+    RPE_CHECK_LAUNCH();
+    return 0;
+}
+
+int rpe_adamw_step_sched(float* p, const float* g, float* m, float* v, float* ema, long n, double lr, double beta1, double beta2, double eps,
+                         double weight_decay, double ema_decay, const float* state, const float* sched, int use_clip, void* stream) {
+    if (n <= 0) return 0;
+    if (!state || !sched) return rpe_set_error(RPE_ERR_SHAPE, "adamw_step_sched: null state or sched");
+    if (ema && !(ema_decay >= 0.0 && ema_decay < 1.0)) return rpe_set_error(RPE_ERR_SHAPE, "adamw_step_sched: ema_decay in [0, 1)");
+    if ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)m) | ((uintptr_t)v) | ((uintptr_t)ema)) & 15)
+        return rpe_set_error(RPE_ERR_ALIGN, "adamw_step_sched: buffers must be 16-byte aligned");
+    const dim3 grid(ew_grid(n / 4 + 1));
+    if (ema)
+        hipLaunchKernelGGL((adamw_sched_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1, beta2, (float)eps, weight_decay,
+                           (float)(1.0 - ema_decay), state, sched, use_clip);
+    else
+        hipLaunchKernelGGL((adamw_sched_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, n, lr, beta1, beta2, (float)eps, weight_decay,
+                           0.f, state, sched, use_clip);
+    RPE_CHECK_LAUNCH();
+    return 0;
+}
+
+int rpe_swap_f32(float* a, float* b, long n, void* stream) {
+    if (n <= 0) return 0;
+    if (!a || !b) return rpe_set_error(RPE_ERR_SHAPE, "swap_f32: null buffer");
+    if ((((uintptr_t)a) | ((uintptr_t)b)) & 15) return rpe_set_error(RPE_ERR_ALIGN, "swap_f32: buffers must be 16-byte aligned");
+    if (a < b + n && b < a + n) return rpe_set_error(RPE_ERR_SHAPE, "swap_f32: the buffers overlap");
+    hipLaunchKernelGGL(swap_f32_kernel, dim3(ew_grid(n / 4 + 1)), dim3(256), 0, (hipStream_t)stream, a, b, n);
     RPE_CHECK_LAUNCH();
     return 0;
 }

@@ -7,7 +7,13 @@ Two options the reference does not have, both off by default and both on the dev
 util.learn_utils.GraphedTrainStep): `max_grad_norm` clips the global gradient norm as torch.nn.utils.clip_grad_norm_ does, and
 `weight_decay` (FusedAdamW) is torch.optim.AdamW's decoupled decay.  The loss is SUMMED over episodes x sequence steps
 (DESIGN.md section 2), so the gradient grows with the batch; the clip bounds the update whatever the batch.
+
+Three more, off by default and on the device as well: `lr_schedule` (LRSchedule: linear warm-up, then constant / cosine / step decay,
+evaluated by rpe_lr_schedule from the device's step count), per-group hyper-parameters (every param group is updated with its own lr,
+betas, eps and weight_decay over its own arena segments) and `ema_decay` (an exponential moving average of the weights, written by the
+update kernel itself).  lr_factor() below is the one statement of the schedule rule.
 """
+import contextlib
 import math
 
 import torch
@@ -24,8 +30,84 @@ def _check_options(weight_decay, max_grad_norm):
         raise ValueError("invalid max_grad_norm %r: None (off) or a value > 0" % (max_grad_norm,))
 
 
+SCHEDULE_KINDS = ("constant", "cosine", "step")     # the `kind` argument of rpe_lr_schedule is the index
+
+
+def _is_int(x):
+    return isinstance(x, int) and not isinstance(x, bool)
+
+
+class LRSchedule:
+    """Linear warm-up over `warmup_steps` optimizer steps from `warmup_start_factor`, then `kind`:
+    constant: 1;  cosine: half a cosine from 1 down to `min_factor` at `total_steps`, held there afterwards;  step: times `gamma` every
+    `step_size` steps after the warm-up.  A validated value object: the position is the optimizer's step count, not kept here."""
+    FIELDS = ("kind", "warmup_steps", "warmup_start_factor", "total_steps", "min_factor", "step_size", "gamma")
+
+    def __init__(self, kind="constant", warmup_steps=0, warmup_start_factor=0.1, total_steps=None, min_factor=0.0, step_size=None, gamma=0.1):
+        if kind not in SCHEDULE_KINDS:
+            raise ValueError("invalid schedule kind %r: one of %s" % (kind, ", ".join(SCHEDULE_KINDS)))
+        if not _is_int(warmup_steps) or warmup_steps < 0:
+            raise ValueError("invalid warmup_steps %r: an integer >= 0" % (warmup_steps,))
+        if not 0.0 <= warmup_start_factor <= 1.0:
+            raise ValueError("invalid warmup_start_factor %r: a value in [0, 1]" % (warmup_start_factor,))
+        if not 0.0 <= min_factor <= 1.0:
+            raise ValueError("invalid min_factor %r: a value in [0, 1]" % (min_factor,))
+        if total_steps is not None and not _is_int(total_steps):
+            raise ValueError("invalid total_steps %r: an integer" % (total_steps,))
+        if kind == "cosine" and (total_steps is None or total_steps <= warmup_steps):
+            raise ValueError("invalid total_steps %r: the cosine schedule needs total_steps > warmup_steps" % (total_steps,))
+        if (step_size is not None or kind == "step") and (not _is_int(step_size) or step_size < 1):
+            raise ValueError("invalid step_size %r: an integer >= 1" % (step_size,))
+        if not 0.0 < gamma <= 1.0:
+            raise ValueError("invalid gamma %r: a value in (0, 1]" % (gamma,))
+        self.kind, self.warmup_steps, self.warmup_start_factor = kind, warmup_steps, float(warmup_start_factor)
+        self.total_steps, self.min_factor, self.step_size, self.gamma = total_steps, float(min_factor), step_size, float(gamma)
+
+    def state_dict(self):
+        return {k: getattr(self, k) for k in self.FIELDS}
+
+    def load_state_dict(self, sd):
+        self.__init__(**{k: sd[k] for k in self.FIELDS})
+
+    def __eq__(self, other):
+        return isinstance(other, LRSchedule) and self.state_dict() == other.state_dict()
+
+    def __repr__(self):
+        return "LRSchedule(%s)" % ", ".join("%s=%r" % kv for kv in self.state_dict().items())
+
+    def c_args(self):
+        """the scalar arguments of rpe_lr_schedule (an unused total_steps / step_size as 0 / 1)"""
+        return (SCHEDULE_KINDS.index(self.kind), self.warmup_steps, self.warmup_start_factor, self.total_steps or 0, self.min_factor,
+                self.step_size or 1, self.gamma)
+
+
+def lr_factor(schedule, e):
+    """The factor that multiplies every group's lr at the optimizer step that follows `e` completed ones (e = 0: the first step), in
+    fp64 -- the closed form rpe_lr_schedule evaluates on the device.  With W = warmup_steps, s = warmup_start_factor, T = total_steps,
+    fmin = min_factor:
+        e < W:     s + (1 - s) e / W                      torch's LinearLR(start_factor=s, total_iters=W)
+        constant:  1
+        cosine:    fmin + (1 - fmin)(1 + cos(pi (min(e, T) - W) / (T - W))) / 2
+                                                          CosineAnnealingLR(T_max=T - W, eta_min=fmin lr) after the warm-up; beyond T
+                                                          it HOLDS fmin (torch's recursion climbs again)
+        step:      gamma ** ((e - W) // step_size)        StepLR after the warm-up"""
+    e = int(e)
+    if e < 0:
+        raise ValueError("lr_factor: e >= 0")
+    W, s = schedule.warmup_steps, schedule.warmup_start_factor
+    if e < W:
+        return s + (1.0 - s) * e / W
+    if schedule.kind == "cosine":
+        T, fmin = schedule.total_steps, schedule.min_factor
+        return fmin + (1.0 - fmin) * (1.0 + math.cos(math.pi * (min(e, T) - W) / (T - W))) / 2.0
+    if schedule.kind == "step":
+        return schedule.gamma ** ((e - W) // schedule.step_size)
+    return 1.0
+
+
 class FusedAdam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, capturable=False, *, weight_decay=0.0, max_grad_norm=None):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, capturable=False, *, weight_decay=0.0, max_grad_norm=None,
+                 lr_schedule=None, ema_decay=None):
         """capturable: keep the step count (for the bias corrections) on the DEVICE, so that a captured hipGraph of the whole
         train step (util.learn_utils.GraphedTrainStep) advances it at every replay; a host-side count would be frozen at its
         capture-time value.  Same update rule either way.
@@ -37,10 +119,32 @@ class FusedAdam(torch.optim.Optimizer):
         last step's values as 0-d device tensors.  inf: measure the norm only.
         weight_decay: decoupled decay, p *= 1 - lr weight_decay before the update (torch.optim.AdamW; see FusedAdamW).  It
         applies to every trainable parameter, BatchNorm weights and biases included, as AdamW(model.parameters()) does.
-        With either option set the step count lives on the device whatever `capturable` says."""
+        With either option set the step count lives on the device whatever `capturable` says.
+
+        lr_schedule: an LRSchedule.  Every group's rate is group["lr"] * lr_factor(lr_schedule, e), e the optimizer steps taken so
+        far, evaluated on the device from the device's step count (a skipped fp16 step does not advance it).  Under
+        GraphedTrainStep a host scheduler (torch.optim.lr_scheduler) that writes group["lr"] is NOT seen by the replays -- the rate
+        is a launch argument the capture froze -- while lr_schedule= is.  In eager mode both compose: the factor multiplies whatever
+        group["lr"] holds.  `lr_factor` and `steps_scheduled` expose the last step's factor and e as 0-d device tensors.
+        ema_decay: in [0, 1): keep ema = decay ema + (1 - decay) p over all trainable parameters, updated from the new p inside the
+        update kernel (torch.optim.swa_utils.get_ema_multi_avg_fn's rule).  It starts as a copy of the arena, so frozen parameters
+        equal themselves; BatchNorm buffers are not averaged (AveragedModel's default does not either).  ema_parameters() is the
+        flat average, averaged_weights(model) swaps it into the model for validation / rollout.
+        Neither is a param-group key: they are attributes, and top-level keys ("lr_schedule", "ema") of state_dict().  With either set
+        the step count lives on the device as well.
+        Param groups: every group is updated with its own lr, betas, eps and weight_decay over its own parameters' segments;
+        max_grad_norm is one global norm and must be the same in all groups."""
         if lr < 0.0 or eps < 0.0 or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError("invalid Adam hyper-parameters")
         _check_options(weight_decay, max_grad_norm)
+        if lr_schedule is not None and not isinstance(lr_schedule, LRSchedule):
+            raise ValueError("invalid lr_schedule %r: None (off) or an LRSchedule" % (lr_schedule,))
+        if ema_decay is not None and not 0.0 <= ema_decay < 1.0:      # < 0, >= 1 or NaN
+            raise ValueError("invalid ema_decay %r: None (off) or a value in [0, 1)" % (ema_decay,))
+        self.lr_schedule, self.ema_decay = lr_schedule, ema_decay
+        self._ema = None            # the fp32 average in arena order (allocated with the moments)
+        self._sched = None          # 4 device floats: factor, steps taken before the last step, -, -
+        self._sched_state = None    # the block the last scheduled step wrote factor and step count to
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm))
         self.capturable = capturable
         self._dev_state = None
@@ -49,6 +153,20 @@ class FusedAdam(torch.optim.Optimizer):
         self._step = 0
         self._m = self._v = None
         self._arena = None
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        g = self.param_groups[-1]
+        try:
+            if g["lr"] < 0.0 or g["eps"] < 0.0 or not (0.0 <= g["betas"][0] < 1.0 and 0.0 <= g["betas"][1] < 1.0):
+                raise ValueError("invalid Adam hyper-parameters in a param group")
+            _check_options(g["weight_decay"], g["max_grad_norm"])
+            norms = {x["max_grad_norm"] for x in self.param_groups}
+            if len(norms) > 1:
+                raise ValueError("max_grad_norm is ONE global norm: every param group must carry the same value, got %s" % sorted(map(repr, norms)))
+        except ValueError:
+            del self.param_groups[-1]
+            raise
 
     def _ensure(self):
         params = [p for g in self.param_groups for p in g["params"]]
@@ -67,6 +185,10 @@ class FusedAdam(torch.optim.Optimizer):
             loaded = self._m is not None and self._m.numel() == arena.flat.numel()   # moments restored by load_state_dict
             self._m = self._m.to(arena.flat.device) if loaded else torch.zeros_like(arena.flat)
             self._v = self._v.to(arena.flat.device) if loaded else torch.zeros_like(arena.flat)
+            if self.ema_decay is not None:
+                loaded = self._ema is not None and self._ema.numel() == arena.flat.numel()   # average restored by load_state_dict
+                self._ema = self._ema.to(arena.flat.device) if loaded else arena.flat.clone()  # a copy: frozen parameters equal themselves
+            self._sched = self._sched_state = None
         return arena
 
     def zero_grad(self, set_to_none=True):
@@ -94,17 +216,63 @@ class FusedAdam(torch.optim.Optimizer):
         """0-d device view of the coefficient the last clipped step multiplied the gradients by (None before the first one)"""
         return None if self._clip_state is None else self._clip_state[7]
 
-    def _step_clip_decay(self, arena, g, scaler, wd, max_norm):
-        """The device-state route with the norm pass and / or the decay: [unscale,] step bump, sum of squares per segment, norm and
-        coefficient, update per segment.  No host synchronisation; nothing is allocated after the first step."""
-        b1, b2 = g["betas"]
+    @property
+    def lr_factor(self):
+        """0-d device view of the factor the last scheduled step multiplied every group's lr by (None before the first one)"""
+        return None if self._sched_state is None else self._sched_state[0]
+
+    @property
+    def steps_scheduled(self):
+        """0-d device view of e, the optimizer steps taken before the last scheduled step (None before the first one)"""
+        return None if self._sched_state is None else self._sched_state[1]
+
+    def ema_parameters(self):
+        """The flat fp32 average in arena order (None without ema_decay, or before the arena exists)"""
+        return self._ema
+
+    def _swap_ema(self, arena):
+        s = ops._stream()
+        for lo, hi in arena.trainable_segments():
+            lib.rpe_swap_f32(ops._p(arena.flat[lo:hi]), ops._p(self._ema[lo:hi]), hi - lo, s)
+
+    @contextlib.contextmanager
+    def averaged_weights(self, model=None):
+        """Inside the block the trainable parameters hold the average (and ema_parameters() the raw weights): an in-place exchange
+        over the trainable segments, undone by the same call on exit, exceptions included.  No address changes, so a captured train
+        step replays correctly afterwards; use it OUTSIDE any capture.  `model`: its trunk is told that the weights changed (the
+        cached compute-dtype / BN-folded copies are stale), on entry and on exit."""
+        if self.ema_decay is None:
+            raise RuntimeError("averaged_weights() needs FusedAdam(..., ema_decay=...)")
+        arena = self._ensure()
+        trunk = getattr(model, "trunk", None)
+        self._swap_ema(arena)
+        if trunk is not None:
+            trunk.weights_changed()
+        try:
+            yield self
+        finally:
+            self._swap_ema(arena)
+            if trunk is not None:
+                trunk.weights_changed()
+
+    def _groups(self, arena):
+        """[(param group, its trainable segments)]; with one group the segments are the arena's, as they always were"""
+        if len(self.param_groups) == 1:
+            return [(self.param_groups[0], arena.trainable_segments())]
+        return [(g, arena.trainable_segments(g["params"])) for g in self.param_groups]
+
+    def _step_device(self, arena, groups, scaler, max_norm):
+        """The device-state route with the norm pass, the decay, the schedule and / or the average: [unscale,] step bump, [sum of
+        squares per segment, norm and coefficient,] [schedule,] update per segment.  No host synchronisation; nothing is allocated
+        after the first step."""
+        scheduled = self.lr_schedule is not None or self.ema_decay is not None
         s = ops._stream()
         if scaler is not None:
             st = scaler.unscale_and_update(arena.grad)                           # fp16: rpe_amp_unscale, rpe_amp_update
         else:
             st = self._device_state(arena)
             lib.rpe_amp_update(ops._p(st), 1.0, 1.0, 1 << 30, s)                 # steps += 1 (found_inf is never set)
-        segs = arena.trainable_segments()
+        segs = [seg for _, gs in groups for seg in gs]
         rows = 0
         if max_norm is not None:
             if self._partials is None or self._partials[0] != segs or self._partials[2].device != arena.grad.device:
@@ -116,11 +284,26 @@ class FusedAdam(torch.optim.Optimizer):
             for (lo, hi), off in zip(segs, offs):
                 lib.rpe_grad_sumsq(ops._p(arena.grad[lo:hi]), hi - lo, ops._p(part[off:]), s)
             rows = offs[-1]
-        lib.rpe_clip_coef(ops._p(self._partials[2] if rows else None), rows, 0.0 if max_norm is None else max_norm, ops._p(st), s)   # st[6], st[7]
+        if max_norm is not None or not scheduled:
+            lib.rpe_clip_coef(ops._p(self._partials[2] if rows else None), rows, 0.0 if max_norm is None else max_norm, ops._p(st), s)   # st[6], st[7]
         use_clip = int(max_norm is not None and math.isfinite(max_norm))
-        for lo, hi in segs:
-            lib.rpe_adamw_step_clip(ops._p(arena.flat[lo:hi]), ops._p(arena.grad[lo:hi]), ops._p(self._m[lo:hi]), ops._p(self._v[lo:hi]), hi - lo,
-                                    g["lr"], b1, b2, g["eps"], wd, ops._p(st), use_clip, s)
+        if scheduled:
+            if self._sched is None or self._sched.device != arena.flat.device:
+                self._sched = torch.tensor([1.0, 0.0, 0.0, 0.0], dtype=torch.float32).to(arena.flat.device)   # factor 1 without a schedule
+            if self.lr_schedule is not None:
+                lib.rpe_lr_schedule(ops._p(st), *self.lr_schedule.c_args(), ops._p(self._sched), s)            # sched[0], sched[1]
+                self._sched_state = self._sched
+        ema, ema_decay = self._ema, 0.0 if self.ema_decay is None else self.ema_decay
+        for g, gs in groups:
+            (b1, b2), wd = g["betas"], g.get("weight_decay", 0.0)
+            for lo, hi in gs:
+                if scheduled:
+                    lib.rpe_adamw_step_sched(ops._p(arena.flat[lo:hi]), ops._p(arena.grad[lo:hi]), ops._p(self._m[lo:hi]), ops._p(self._v[lo:hi]),
+                                             ops._p(None if ema is None else ema[lo:hi]), hi - lo, g["lr"], b1, b2, g["eps"], wd, ema_decay,
+                                             ops._p(st), ops._p(self._sched), use_clip, s)
+                else:
+                    lib.rpe_adamw_step_clip(ops._p(arena.flat[lo:hi]), ops._p(arena.grad[lo:hi]), ops._p(self._m[lo:hi]), ops._p(self._v[lo:hi]), hi - lo,
+                                            g["lr"], b1, b2, g["eps"], wd, ops._p(st), use_clip, s)
         if max_norm is not None:
             self._clip_state = st
         return None
@@ -138,36 +321,36 @@ class FusedAdam(torch.optim.Optimizer):
     def step(self, closure=None):
         arena = self._ensure()
         self._step += 1
-        g = self.param_groups[0]
-        b1, b2 = g["betas"]
+        groups = self._groups(arena)
         scaler = getattr(arena, "loss_scaler", None)
-        wd, max_norm = g.get("weight_decay", 0.0), g.get("max_grad_norm")
-        if wd or max_norm is not None:
-            return self._step_clip_decay(arena, g, scaler, wd, max_norm)
+        max_norm = self.param_groups[0].get("max_grad_norm")
+        if max_norm is not None or self.lr_schedule is not None or self.ema_decay is not None or any(g.get("weight_decay", 0.0) for g, _ in groups):
+            return self._step_device(arena, groups, scaler, max_norm)
         if scaler is not None:
             # fp16 compute (amp.py): unscale + finite check, scale update and the skip decision all stay on the device; the
             # bias-correction step count is the device's count of steps actually taken (self._step counts calls)
             st = scaler.unscale_and_update(arena.grad)
             s = ops._stream()
-            for lo, hi in arena.trainable_segments():
-                lib.rpe_adam_step_amp(ops._p(arena.flat[lo:hi]), ops._p(arena.grad[lo:hi]), ops._p(self._m[lo:hi]), ops._p(self._v[lo:hi]), hi - lo,
-                                      g["lr"], b1, b2, g["eps"], ops._p(st), s)
+            for g, segs in groups:
+                b1, b2 = g["betas"]
+                for lo, hi in segs:
+                    lib.rpe_adam_step_amp(ops._p(arena.flat[lo:hi]), ops._p(arena.grad[lo:hi]), ops._p(self._m[lo:hi]), ops._p(self._v[lo:hi]), hi - lo,
+                                          g["lr"], b1, b2, g["eps"], ops._p(st), s)
             return None
         if self.capturable:
-            # device-side step count: the same state block the loss scaler uses (amp.py), with scale 1 and no unscale pass
-            if self._dev_state is None or self._dev_state.device != arena.flat.device:
-                st = torch.zeros(8, dtype=torch.float32)
-                st[0] = st[1] = 1.0
-                st[5] = float(self._step - 1)
-                self._dev_state = st.to(arena.flat.device)
+            st = self._device_state(arena)
             s = ops._stream()
-            lib.rpe_amp_update(ops._p(self._dev_state), 1.0, 1.0, 1 << 30, s)   # steps += 1 (found_inf is never set)
-            for lo, hi in arena.trainable_segments():
-                lib.rpe_adam_step_amp(ops._p(arena.flat[lo:hi]), ops._p(arena.grad[lo:hi]), ops._p(self._m[lo:hi]), ops._p(self._v[lo:hi]), hi - lo,
-                                      g["lr"], b1, b2, g["eps"], ops._p(self._dev_state), s)
+            lib.rpe_amp_update(ops._p(st), 1.0, 1.0, 1 << 30, s)   # steps += 1 (found_inf is never set)
+            for g, segs in groups:
+                b1, b2 = g["betas"]
+                for lo, hi in segs:
+                    lib.rpe_adam_step_amp(ops._p(arena.flat[lo:hi]), ops._p(arena.grad[lo:hi]), ops._p(self._m[lo:hi]), ops._p(self._v[lo:hi]), hi - lo,
+                                          g["lr"], b1, b2, g["eps"], ops._p(st), s)
             return None
-        for lo, hi in arena.trainable_segments():
-            ops.adam_step(arena.flat[lo:hi], arena.grad[lo:hi], self._m[lo:hi], self._v[lo:hi], g["lr"], b1, b2, g["eps"], self._step)
+        for g, segs in groups:
+            b1, b2 = g["betas"]
+            for lo, hi in segs:
+                ops.adam_step(arena.flat[lo:hi], arena.grad[lo:hi], self._m[lo:hi], self._v[lo:hi], g["lr"], b1, b2, g["eps"], self._step)
         return None
 
     def state_dict(self):
@@ -180,12 +363,21 @@ class FusedAdam(torch.optim.Optimizer):
         scaler = getattr(self._arena, "loss_scaler", None) if self._arena is not None else None
         if scaler is not None:
             sd["amp"] = scaler.state_dict()
+        # the schedule's position is the device-side step count above; the average is saved like the moments
+        if self.lr_schedule is not None:
+            sd["lr_schedule"] = self.lr_schedule.state_dict()
+        if self.ema_decay is not None:
+            sd["ema"] = self._ema
         return sd
 
     def load_state_dict(self, sd):
         self._step = int(sd["step"])
         self._m = None if sd["m"] is None else sd["m"].clone()
         self._v = None if sd["v"] is None else sd["v"].clone()
+        # a checkpoint without these keys keeps the constructor's schedule, and the average starts from the weights
+        if sd.get("lr_schedule") is not None:
+            self.lr_schedule = LRSchedule(**sd["lr_schedule"])
+        self._ema = sd["ema"].clone() if self.ema_decay is not None and sd.get("ema") is not None else None
         self._arena = None   # re-attached (and the moments moved to its device) at the next step
         self._dev_state = sd["dev_state"].clone() if sd.get("dev_state") is not None else None
         # fp16: the loss scaler must hold the checkpointed scale BEFORE the first backward after the resume multiplies the output
@@ -211,5 +403,7 @@ class FusedAdam(torch.optim.Optimizer):
 class FusedAdamW(FusedAdam):
     """FusedAdam with torch.optim.AdamW's default decoupled weight decay of 1e-2 (what fine-tuning a pretrained trunk expects)."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, capturable=False, *, weight_decay=1e-2, max_grad_norm=None):
-        super().__init__(params, lr=lr, betas=betas, eps=eps, capturable=capturable, weight_decay=weight_decay, max_grad_norm=max_grad_norm)
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, capturable=False, *, weight_decay=1e-2, max_grad_norm=None,
+                 lr_schedule=None, ema_decay=None):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, capturable=capturable, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                         lr_schedule=lr_schedule, ema_decay=ema_decay)

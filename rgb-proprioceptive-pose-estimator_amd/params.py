@@ -71,11 +71,17 @@ class ParamArena:
             else:
                 p.grad = None
 
-    def trainable_segments(self):
-        """Merged [start, end) ranges of the flat buffer that belong to requires_grad parameters."""
+    def trainable_segments(self, params=None):
+        """Merged [start, end) ranges of the flat buffer that belong to requires_grad parameters; with `params` (an optimizer's
+        parameter group), of those parameters only -- every one of them must live in this arena."""
+        only = None
+        if params is not None:
+            only = {id(p) for p in params}
+            if not only <= {id(p) for p in self.params}:
+                raise ValueError("trainable_segments: a parameter that is not in this arena")
         segs = []
         for p, off in zip(self.params, self.offsets):
-            if not p.requires_grad:
+            if not p.requires_grad or (only is not None and id(p) not in only):
                 continue
             end = off + _pad4(p.numel())
             if segs and segs[-1][1] == off:

@@ -5,7 +5,9 @@ Keeps every flag of the reference's scripts/train_model.py:17-47 (names, types, 
 dispatch (:158-218), criterion dict (:100-105), Adam (:228) and train() call (:248-259).  The Robosuite environment
 the reference builds at import time (:84-97) is replaced by seeded synthetic Robosuite-shaped episodes; flags that only
 configure the simulator (--controller, --robots, --use_placement_initializer, --motion) are accepted and recorded.
-Added flags: --dtype {bf16,f16,f32}, --optimizer {fused,torch}, --max_grad_norm, --weight_decay, --episodes_seed.
+Added flags: --dtype {bf16,f16,f32}, --optimizer {fused,torch}, --max_grad_norm, --weight_decay, --episodes_seed; the on-device
+learning-rate schedule (--lr_schedule, --warmup_steps, --warmup_start_factor, --lr_total_steps, --lr_min_factor, --lr_step_size,
+--lr_gamma), --trunk_lr_scale (the trunk as a param group of its own) and --ema_decay (writes `<checkpoint>.ema` beside the raw weights).
 
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 scripts/train_model.py ...`;
 episodes are sharded over ranks and gradients SUM-all-reduced over RCCL.
@@ -61,6 +63,17 @@ def build_parser():
     p.add_argument("--max_grad_norm", type=float, default=None,
                    help="clip the global gradient norm to this value on the device before the Adam update (default: off; needs --optimizer fused)")
     p.add_argument("--weight_decay", type=float, default=0.0, help="decoupled weight decay (AdamW; default 0 = plain Adam)")
+    p.add_argument("--lr_schedule", choices=["constant", "cosine", "step"], default=None,
+                   help="learning-rate schedule evaluated on the device (optim.LRSchedule; default: none; needs --optimizer fused, like the flags below)")
+    p.add_argument("--warmup_steps", type=int, default=None, help="linear warm-up over this many optimizer steps (default 0)")
+    p.add_argument("--warmup_start_factor", type=float, default=None, help="the warm-up starts at lr times this (default 0.1)")
+    p.add_argument("--lr_total_steps", type=int, default=None, help="cosine: the step at which lr reaches lr * lr_min_factor (required for cosine)")
+    p.add_argument("--lr_min_factor", type=float, default=None, help="cosine: the final factor (default 0)")
+    p.add_argument("--lr_step_size", type=int, default=None, help="step: multiply lr by lr_gamma every this many steps after the warm-up")
+    p.add_argument("--lr_gamma", type=float, default=None, help="step: the factor (default 0.1)")
+    p.add_argument("--trunk_lr_scale", type=float, default=None, help="train the ResNet trunk at lr times this, as a param group of its own (default: one group)")
+    p.add_argument("--ema_decay", type=float, default=None,
+                   help="keep an exponential moving average of the weights on the device, validate with it and save it as <checkpoint>.ema (default: off)")
     p.add_argument("--episodes_seed", type=int, default=1234, help="seed of the synthetic episode generator")
     p.add_argument("--no_save", action="store_true", help="do not write the best-validation checkpoint")
     p.add_argument("--episodes", type=str, default=None, metavar="FILE.npz",
@@ -97,17 +110,51 @@ def build_model(args, compute_dtype):
                                                        proprio_hidden_dim=args.proprio_hidden_dim, **common)
 
 
+SCHEDULE_FLAGS = ("lr_schedule", "warmup_steps", "warmup_start_factor", "lr_total_steps", "lr_min_factor", "lr_step_size", "lr_gamma")
+FUSED_ONLY_FLAGS = SCHEDULE_FLAGS + ("trunk_lr_scale", "ema_decay")
+
+
+def build_schedule(args):
+    """the --lr_schedule family -> optim.LRSchedule, or None when none of its flags is given (a warm-up alone is a constant schedule)"""
+    from rgb_proprioceptive_pose_estimator_amd.optim import LRSchedule
+    given = {k: getattr(args, k, None) for k in SCHEDULE_FLAGS}
+    if all(v is None for v in given.values()):
+        return None
+    kind = given["lr_schedule"] or "constant"
+    if kind == "cosine" and given["lr_total_steps"] is None:
+        raise SystemExit("--lr_schedule cosine needs --lr_total_steps")
+    if kind == "step" and given["lr_step_size"] is None:
+        raise SystemExit("--lr_schedule step needs --lr_step_size")
+    kw = dict(warmup_steps=given["warmup_steps"], warmup_start_factor=given["warmup_start_factor"], total_steps=given["lr_total_steps"],
+              min_factor=given["lr_min_factor"], step_size=given["lr_step_size"], gamma=given["lr_gamma"])
+    return LRSchedule(kind, **{k: v for k, v in kw.items() if v is not None})
+
+
 def build_optimizer(args, params):
-    """--optimizer / --max_grad_norm / --weight_decay -> FusedAdam, FusedAdamW, torch.optim.Adam or torch.optim.AdamW"""
+    """--optimizer / --max_grad_norm / --weight_decay / the schedule flags / --ema_decay -> FusedAdam, FusedAdamW, torch.optim.Adam or
+    torch.optim.AdamW.  params: parameters, or group dicts (util.model_utils.lr_param_groups: a group's `lr_scale` becomes lr * scale)."""
     from rgb_proprioceptive_pose_estimator_amd.optim import FusedAdam, FusedAdamW
     if args.dtype == "f16" and args.optimizer != "fused":
         raise SystemExit("--dtype f16 needs --optimizer fused: the loss-scale unscale / skip logic lives in FusedAdam.step (amp.py)")
     if args.max_grad_norm is not None and args.optimizer != "fused":
         raise SystemExit("--max_grad_norm needs --optimizer fused: the on-device norm and clip live in FusedAdam.step (optim.py)")
+    for flag in FUSED_ONLY_FLAGS:
+        if getattr(args, flag, None) is not None and args.optimizer != "fused":
+            raise SystemExit("--%s needs --optimizer fused: the on-device schedule, the per-group update and the weight average live in "
+                             "FusedAdam.step (optim.py)" % flag)
+    params = list(params)
+    if params and isinstance(params[0], dict):
+        params = [dict({k: v for k, v in g.items() if k != "lr_scale"}, **({"lr": args.lr * g["lr_scale"]} if "lr_scale" in g else {})) for g in params]
+    extra = {}
+    schedule, ema_decay = build_schedule(args), getattr(args, "ema_decay", None)
+    if schedule is not None:
+        extra["lr_schedule"] = schedule
+    if ema_decay is not None:
+        extra["ema_decay"] = ema_decay
     if args.optimizer == "fused":
         if args.weight_decay:
-            return FusedAdamW(params, lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm)
-        return FusedAdam(params, lr=args.lr, max_grad_norm=args.max_grad_norm)
+            return FusedAdamW(params, lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm, **extra)
+        return FusedAdam(params, lr=args.lr, max_grad_norm=args.max_grad_norm, **extra)
     if args.weight_decay:
         return torch.optim.AdamW(params, lr=args.lr, weight_decay=args.weight_decay)
     return torch.optim.Adam(params, lr=args.lr)
@@ -119,6 +166,7 @@ def main(argv=None):
     from rgb_proprioceptive_pose_estimator_amd.models import PoseDistanceLoss
     from rgb_proprioceptive_pose_estimator_amd.util.data_utils import RecordedEpisodeDataset, SyntheticEpisodeDataset
     from rgb_proprioceptive_pose_estimator_amd.util.learn_utils import train
+    from rgb_proprioceptive_pose_estimator_amd.util.model_utils import lr_param_groups
 
     rank, world, local = init_from_env()
     if not torch.cuda.is_available():
@@ -138,7 +186,7 @@ def main(argv=None):
     model = build_model(args, DTYPES[args.dtype])
     if args.load_checkpoint:
         model.load_state_dict(torch.load(args.checkpoint_model_path, map_location="cpu"))
-    optimizer = build_optimizer(args, model.parameters())
+    optimizer = build_optimizer(args, lr_param_groups(model, args.trunk_lr_scale))
     if args.episodes:
         dataset = RecordedEpisodeDataset(args.episodes, use_depth=args.use_depth, obj_name=args.obj_name, seed=args.episodes_seed + 1000 * rank)
         if args.horizon != build_parser().get_default("horizon") and args.horizon != dataset.env.horizon and rank == 0:

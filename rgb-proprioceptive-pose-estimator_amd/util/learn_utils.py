@@ -13,6 +13,7 @@ rollout() of the reference needs the simulator and is out of scope (SURVEY.md se
 walked step by step, per-step position / orientation errors, their per-episode and overall statistics (util/learn_utils.py:
 446-538) -- is `evaluate_episodes`: all episodes advance together as lanes of one batch and the errors stay on the device.
 """
+import contextlib
 import copy
 import os
 import time
@@ -381,12 +382,19 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
           save_path='default', save_model=True, logging=True, *, save_optimizer=False):
     """See the module docstring.  Returns (model with the best validation weights, best validation loss).
     save_optimizer (addition; the reference saves weights only): also write `<save_path>.optim` with the optimizer state of the
-    best-validation epoch so that a run can be resumed (`optimizer.load_state_dict(torch.load(path))`)."""
+    best-validation epoch so that a run can be resumed (`optimizer.load_state_dict(torch.load(path))`).
+    An optimizer with a weight average (FusedAdam(ema_decay=...)): the `val` phase runs on the AVERAGED weights, so the best
+    validation loss is theirs, and beside `<save_path>` (the raw weights, unchanged: a resume with `.optim` continues exactly)
+    `<save_path>.ema` holds model.state_dict() with the averaged weights -- reference-shaped, so scripts/rollout.py
+    --checkpoint_model_path X.ema loads it as it is.  BatchNorm's running statistics are not averaged: `.ema` carries those of the
+    raw run.  With a schedule (lr_schedule=...) the per-epoch train line shows the current rate of the first param group."""
     train_obj_pose = hasattr(model, "object_name")
     dt_string = datetime.now().strftime("%d-%m-%Y_%H-%M-%S")
     since = time.time()
     best_model = copy.deepcopy(model.state_dict())
     best_err = np.inf
+    has_ema = getattr(optimizer, "ema_decay", None) is not None
+    scheduled = getattr(optimizer, "lr_schedule", None) is not None
     rank = dist.get_rank() if dist.is_initialized() else 0
     world = dist.get_world_size() if dist.is_initialized() else 1
     writer = _writer(logging and rank == 0)
@@ -419,22 +427,30 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
             clip_sums = torch.zeros(2, dtype=torch.float64, device="cuda") if phase == "train" and getattr(optimizer, "max_grad_norm", None) is not None else None
             clip_steps = 0
             horizon = len(dataset)
-            for img, depth, x0bar, x0, x1, obj in _chunks(dataset, horizon, seq, model.use_depth if hasattr(model, "use_depth") else False):
-                if not model.requires_sequence:  # the reference squeezes the leading batch-of-1 dim (learn_utils.py:141-149)
-                    img, x0bar, x0 = img[0], x0bar[0], x0[0]
-                    depth = None if depth is None else depth[0]
-                    x1 = None if x1 is None else x1[0]
-                    obj = None if obj is None else obj[0]
-                loss, pe, oe = train_step(model, (img, depth, x0bar, x0, x1, obj), criterion, optimizer, train_obj_pose, phase, grad_sync)
-                sums += torch.stack([loss.double(), pe.double(), oe.double()])
-                if clip_sums is not None:
-                    clip_sums += torch.stack([optimizer.grad_norm.double(), (optimizer.clip_coef < 1.0).double()])
-                    clip_steps += 1
-            if world > 1:
-                dist.all_reduce(sums)
-            tot = (sums if clip_sums is None else torch.cat([sums, clip_sums])).tolist()  # the one host synchronisation of the phase
-            denom = horizon * num_episodes
-            epoch_loss, epoch_pos_err, epoch_ori_err = tot[0] / denom, tot[1] / denom, tot[2] / denom
+            ema_sd = None
+            with optimizer.averaged_weights(model) if phase == "val" and has_ema else contextlib.nullcontext():   # validate the average
+                for img, depth, x0bar, x0, x1, obj in _chunks(dataset, horizon, seq, model.use_depth if hasattr(model, "use_depth") else False):
+                    if not model.requires_sequence:  # the reference squeezes the leading batch-of-1 dim (learn_utils.py:141-149)
+                        img, x0bar, x0 = img[0], x0bar[0], x0[0]
+                        depth = None if depth is None else depth[0]
+                        x1 = None if x1 is None else x1[0]
+                        obj = None if obj is None else obj[0]
+                    loss, pe, oe = train_step(model, (img, depth, x0bar, x0, x1, obj), criterion, optimizer, train_obj_pose, phase, grad_sync)
+                    sums += torch.stack([loss.double(), pe.double(), oe.double()])
+                    if clip_sums is not None:
+                        clip_sums += torch.stack([optimizer.grad_norm.double(), (optimizer.clip_coef < 1.0).double()])
+                        clip_steps += 1
+                if world > 1:
+                    dist.all_reduce(sums)
+                stats = [sums] + ([] if clip_sums is None else [clip_sums])
+                if phase == "train" and scheduled and optimizer.lr_factor is not None:
+                    stats.append(optimizer.lr_factor.double().reshape(1))
+                tot = (sums if len(stats) == 1 else torch.cat(stats)).tolist()  # the one host synchronisation of the phase
+                denom = horizon * num_episodes
+                epoch_loss, epoch_pos_err, epoch_ori_err = tot[0] / denom, tot[1] / denom, tot[2] / denom
+                if phase == "val" and has_ema and epoch_loss < best_err and save_model and rank == 0:
+                    ema_sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}   # taken under the swap
+            cur_lr = optimizer.param_groups[0]["lr"] * tot[-1] if phase == "train" and scheduled and optimizer.lr_factor is not None else None
             time_elapsed = time.time() - since
             if writer is not None:
                 tag = "train" if phase == "train" else "val"
@@ -444,9 +460,12 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
                 if clip_sums is not None and clip_steps:   # every rank clips the same reduced gradient: rank 0's figures are everyone's
                     writer.add_scalar("GradNorm/" + tag, tot[3] / clip_steps, epoch)
                     writer.add_scalar("GradClipped/" + tag, tot[4] / clip_steps, epoch)
+                if cur_lr is not None:
+                    writer.add_scalar("LR/" + tag, cur_lr, epoch)
             if logging and rank == 0:
                 print('{} Loss: {:.4f}, PosErr: {:.4f}, OriErr: {:.4f}. Time elapsed = {:.0f}m {:.0f}s'.format(
-                    phase, epoch_loss, epoch_pos_err, epoch_ori_err, time_elapsed // 60, time_elapsed % 60))
+                    phase, epoch_loss, epoch_pos_err, epoch_ori_err, time_elapsed // 60, time_elapsed % 60)
+                    + ("" if cur_lr is None else " lr = {:.3e}".format(cur_lr)))
             if phase == "val" and epoch_loss < best_err:
                 best_err = epoch_loss
                 best_model = copy.deepcopy(model.state_dict())
@@ -455,6 +474,8 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
                         save_path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "log", "runs", fname)
                     os.makedirs(os.path.dirname(os.path.abspath(save_path)), exist_ok=True)
                     torch.save(model.state_dict(), save_path)
+                    if ema_sd is not None:
+                        torch.save(ema_sd, save_path + ".ema")
                     if save_optimizer:
                         torch.save(optimizer.state_dict(), save_path + ".optim")
     if logging and rank == 0:

@@ -65,6 +65,22 @@ def import_resnet(num_layers, output_dim, feature_extract=True, use_pretrained=T
     return model, 224
 
 
+def lr_param_groups(model, trunk_lr_scale=None):
+    """What the optimizer is built over (addition; the reference passes model.parameters(): scripts/train_model.py:228).  No scale, or a
+    scale of 1: the plain parameter list.  Otherwise two groups that partition model.parameters() exactly once, in its order: the
+    ResNet trunk's parameters with `lr_scale` = trunk_lr_scale (scripts.train_model.build_optimizer turns it into lr * scale), and
+    everything else.  The unregistered early-feature heads of the `td` model are not in model.parameters(), so no optimizer has
+    ever seen them, and they are in neither group."""
+    params = list(model.parameters())
+    if trunk_lr_scale is None or trunk_lr_scale == 1:
+        return params
+    if not trunk_lr_scale > 0.0:
+        raise ValueError("invalid trunk_lr_scale %r: a value > 0" % (trunk_lr_scale,))
+    trunk = {id(p) for p in model.trunk.parameters()}
+    groups = [{"params": [p for p in params if id(p) in trunk], "lr_scale": float(trunk_lr_scale)}, {"params": [p for p in params if id(p) not in trunk]}]
+    return [g for g in groups if g["params"]]
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------
 # layer capture / visualisation (util/model_utils.py:10-107 of the reference)
 # ---------------------------------------------------------------------------------------------------------------------------------
