@@ -248,6 +248,27 @@ int rpe_stage_frames_u8_resized(int dtype, const unsigned char* frames, void* ou
 int rpe_stage_depth_f32_resized(const float* frames, float* out, int B, int Hs, int Ws, int Hr, int Wr, int top, int left, int H, int W,
                                 const int* xb, const double* xk, int ksx, const int* yb, const double* yk, int ksy, void* stream);
 
+/* Label-preserving augmentation of raw camera frames (no counterpart in the reference, whose transform is deterministic): photometric
+ * jitter, sensor noise and random erasing on uint8 [B][Hs][Ws][3] frames, uint8 out, in front of rpe_stage_frames_u8[_resized].  All
+ * arithmetic is integer and specified to the bit ("Frame augmentation"); random numbers are Philox4x32-10 keyed by
+ * `seed` with the counter (a, b, step, purpose), bounded draws are (r * n) >> 32. */
+typedef struct {
+    unsigned long long seed;
+    int qb_lo, qb_hi, qc_lo, qc_hi, qs_lo, qs_hi; /* brightness / contrast / saturation factor ranges in Q16: 65536 = identity, 0 <= lo <= hi <= 4 * 65536 */
+    int noise_q;                                  /* Q16 multiplier on the centred sum of four random bytes, 0 = off, at most 4 * 65536 */
+    unsigned erase_thresh;                        /* a stream erases iff its word r < erase_thresh (probability * 2^32, capped at 2^32 - 1); 0 = off */
+    int eh_lo, eh_hi, ew_lo, ew_hi;               /* rectangle height / width bounds in pixels, 1 <= lo <= hi <= Hs / Ws */
+    int fill_mode;                                /* 0: fill_rgb, 1: random bytes */
+    unsigned char fill_rgb[3];
+    int group;                                    /* 0: frame b draws its parameters from stream b; N > 0: from stream b % N */
+} rpe_augment_desc;
+/* in / out: device, [B][Hs][Ws][3], the same buffer or disjoint ones; Hs * Ws < 2^32.  state: device, state[0] is the step counter --
+ * the launch reads it and advances it by one, so a captured call draws fresh numbers at every replay.  params: device, 1 + 8 G ints
+ * (G = B, or `group`), receives [0] = the step used, then per stream qb, qc, qs, erase, top, left, h, w.  sums: device, B entries,
+ * receives each frame's sum of grey values after the brightness stage (untouched when the contrast range is {65536}). */
+int rpe_augment_frames_u8(const unsigned char* in, unsigned char* out, int B, int Hs, int Ws, const rpe_augment_desc* d, unsigned* state, int* params,
+                          unsigned long long* sums, void* stream);
+
 /* ------------------------------------------------------------------ batch norm */
 /* replaces: nn.BatchNorm2d (train mode: biased batch variance, eps, momentum with
  * unbiased running variance) + the in-place nn.ReLU and `out += identity` of the

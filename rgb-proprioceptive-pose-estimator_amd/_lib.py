@@ -36,6 +36,13 @@ class ConvDesc(Structure):
     _fields_ = [(n, c_int) for n in ("batch", "in_h", "in_w", "in_c", "out_c", "kh", "kw", "stride", "pad")]
 
 
+class AugmentDesc(Structure):
+    """rpe_augment_desc"""
+    _fields_ = ([("seed", ctypes.c_ulonglong)] + [(n, c_int) for n in ("qb_lo", "qb_hi", "qc_lo", "qc_hi", "qs_lo", "qs_hi", "noise_q")]
+                + [("erase_thresh", ctypes.c_uint)] + [(n, c_int) for n in ("eh_lo", "eh_hi", "ew_lo", "ew_hi", "fill_mode")]
+                + [("fill_rgb", ctypes.c_ubyte * 3), ("group", c_int)])
+
+
 P, I, L, F, D = c_void_p, c_int, c_long, c_float, c_double
 PD = POINTER(ConvDesc)
 
@@ -84,6 +91,7 @@ _SPEC = {
     "rpe_stage_frames_u8": (I, [I, P, P, I, I, I, I, I, POINTER(c_float), POINTER(c_float), P]),
     "rpe_stage_frames_u8_resized": (I, [I, P, P, I, I, I, I, I, I, I, I, I, P, P, I, P, P, I, P, POINTER(c_float), POINTER(c_float), P]),
     "rpe_stage_depth_f32_resized": (I, [P, P, I, I, I, I, I, I, I, I, I, P, P, I, P, P, I, P]),
+    "rpe_augment_frames_u8": (I, [P, P, I, I, I, POINTER(AugmentDesc), P, P, P, P]),
     "rpe_bn_finalize": (I, [P, I, I, L, P, P, P, P, P, F, F, P, P, P, P, P, P]),
     "rpe_bn_eval_affine": (I, [I, P, P, P, P, F, P, P, P]),
     "rpe_bn_apply": (I, [I, P, P, P, P, P, L, I, I, P]),

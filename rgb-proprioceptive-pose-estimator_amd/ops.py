@@ -698,3 +698,63 @@ def stage_depth(raw, crop_hw=(224, 224), size=256):
         raise ValueError("frames of %dx%d resize to %dx%d, smaller than the %dx%d crop" % (hs, ws, hr, wr, h, w))
     top, left = crop_origin(hr, wr, h, w)
     return stage_depth_window(raw.contiguous(), hr, wr, top, left, h, w)
+
+
+AUGMENT_DESC_FIELDS = ("seed", "qb_lo", "qb_hi", "qc_lo", "qc_hi", "qs_lo", "qs_hi", "noise_q", "erase_thresh", "eh_lo", "eh_hi", "ew_lo", "ew_hi",
+                       "fill_mode", "fill_r", "fill_g", "fill_b", "group")
+
+
+def augment_desc(seed=0, qb_lo=65536, qb_hi=65536, qc_lo=65536, qc_hi=65536, qs_lo=65536, qs_hi=65536, noise_q=0, erase_thresh=0, eh_lo=1, eh_hi=1,
+                 ew_lo=1, ew_hi=1, fill_mode=0, fill_r=124, fill_g=116, fill_b=104, group=0):
+    """rpe_augment_desc from plain integers (the defaults are the identity settings); AUGMENT_DESC_FIELDS is the order of the flat
+    list form `torch.ops.rpe.augment_frames_u8` takes"""
+    from ._lib import AugmentDesc
+    d = AugmentDesc()
+    d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    for k, v in (("qb_lo", qb_lo), ("qb_hi", qb_hi), ("qc_lo", qc_lo), ("qc_hi", qc_hi), ("qs_lo", qs_lo), ("qs_hi", qs_hi), ("noise_q", noise_q),
+                 ("erase_thresh", erase_thresh), ("eh_lo", eh_lo), ("eh_hi", eh_hi), ("ew_lo", ew_lo), ("ew_hi", ew_hi), ("fill_mode", fill_mode),
+                 ("group", group)):
+        setattr(d, k, int(v))
+    for i, v in enumerate((fill_r, fill_g, fill_b)):
+        if not 0 <= int(v) <= 255:
+            raise ValueError("augment_desc: the fill colour is three bytes; got %r" % ((fill_r, fill_g, fill_b),))
+        d.fill_rgb[i] = int(v)
+    return d
+
+
+def augment_streams(desc, b):
+    """number of parameter streams of a batch of b frames"""
+    return desc.group if desc.group > 0 else b
+
+
+def augment_frames_u8(frames, desc, state, out=None, params=None, sums=None):
+    """frames uint8 (..., Hs, Ws, 3) contiguous -> the augmented frames, uint8 of the same shape (rpe_augment_frames_u8: brightness,
+    contrast, saturation, noise, erasing in integer arithmetic).  desc: augment_desc(...).  state: int32 device tensor whose element 0
+    is the step counter; the launch advances it by one.  out: destination (may be `frames` itself).  params / sums: int32 (1 + 8 G,) /
+    int64 (B,) device tensors receiving the parameter table and the per-frame grey sums (allocated when not given)."""
+    if frames.dtype != torch.uint8 or frames.dim() < 4 or frames.shape[-1] != 3:
+        raise ValueError("augment_frames_u8: frames must be uint8 (..., Hs, Ws, 3); got %s %r" % (frames.dtype, tuple(frames.shape)))
+    _chk(frames, "frames")
+    hs, ws = frames.shape[-3:-1]
+    b = frames.numel() // (hs * ws * 3)
+    if b == 0:
+        raise ValueError("augment_frames_u8: empty batch")
+    g = augment_streams(desc, b)
+    dev = frames.device
+    if state.dtype != torch.int32 or state.numel() < 1 or state.device != dev:
+        raise ValueError("augment_frames_u8: state must be an int32 tensor on the frames' device")
+    if out is None:
+        out = torch.empty_like(frames)
+    elif out.dtype != torch.uint8 or out.shape != frames.shape or out.device != dev:
+        raise ValueError("augment_frames_u8: out must be uint8 of the frames' shape on their device")
+    _chk(out, "out")
+    if params is None:
+        params = torch.empty(1 + 8 * g, dtype=torch.int32, device=dev)
+    elif params.dtype != torch.int32 or params.numel() < 1 + 8 * g or params.device != dev:
+        raise ValueError("augment_frames_u8: params must be int32 with at least %d elements" % (1 + 8 * g))
+    if sums is None:
+        sums = torch.empty(b, dtype=torch.int64, device=dev)
+    elif sums.dtype != torch.int64 or sums.numel() < b or sums.device != dev:
+        raise ValueError("augment_frames_u8: sums must be int64 with at least %d elements" % b)
+    lib.rpe_augment_frames_u8(_p(frames), _p(out), b, hs, ws, ctypes.byref(desc), _p(state), _p(_chk(params, "params")), _p(_chk(sums, "sums")), _stream())
+    return out

@@ -7,7 +7,9 @@ the reference builds at import time (:84-97) is replaced by seeded synthetic Rob
 configure the simulator (--controller, --robots, --use_placement_initializer, --motion) are accepted and recorded.
 Added flags: --dtype {bf16,f16,f32}, --optimizer {fused,torch}, --max_grad_norm, --weight_decay, --episodes_seed; the on-device
 learning-rate schedule (--lr_schedule, --warmup_steps, --warmup_start_factor, --lr_total_steps, --lr_min_factor, --lr_step_size,
---lr_gamma), --trunk_lr_scale (the trunk as a param group of its own) and --ema_decay (writes `<checkpoint>.ema` beside the raw weights).
+--lr_gamma), --trunk_lr_scale (the trunk as a param group of its own) and --ema_decay (writes `<checkpoint>.ema` beside the raw weights);
+the on-device frame augmentation of recorded episodes (--aug_brightness, --aug_contrast, --aug_saturation, --aug_noise_std,
+--aug_erase_prob, --aug_erase_scale, --aug_erase_fill, --aug_per_frame, --aug_seed; all off by default, they need --episodes).
 
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 scripts/train_model.py ...`;
 episodes are sharded over ranks and gradients SUM-all-reduced over RCCL.
@@ -79,7 +81,45 @@ def build_parser():
     p.add_argument("--episodes", type=str, default=None, metavar="FILE.npz",
                    help="recorded raw episodes (util.data_utils.RecordedEpisodeDataset: imgs uint8 (E,T,Hs,Ws,3), depths float32 (E,T,Hs,Ws,1), "
                         "true_self / true_other / true_obj (E,T,7)) instead of synthetic ones; the horizon is the file's")
+    p.add_argument("--aug_brightness", type=float, default=None, help="augmentation (needs --episodes): brightness factor in [max(0, 1 - b), 1 + b] (default: off)")
+    p.add_argument("--aug_contrast", type=float, default=None, help="augmentation: contrast factor range, as --aug_brightness (default: off)")
+    p.add_argument("--aug_saturation", type=float, default=None, help="augmentation: saturation factor range, as --aug_brightness (default: off)")
+    p.add_argument("--aug_noise_std", type=float, default=None, help="augmentation: sensor noise, standard deviation in grey levels (default: off)")
+    p.add_argument("--aug_erase_prob", type=float, default=None, help="augmentation: probability of erasing one rectangle per frame (default: off)")
+    p.add_argument("--aug_erase_scale", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="augmentation: each side of the erased rectangle as a fraction of the frame's (default 0.1 0.3)")
+    p.add_argument("--aug_erase_fill", type=str, default=None, help="augmentation: 'mean' (ImageNet mean, the default), 'noise' (random bytes) or R,G,B bytes")
+    p.add_argument("--aug_per_frame", action="store_true",
+                   help="augmentation: draw jitter and occluder per frame (default: per episode, kept through a chunk of --sequence_length steps)")
+    p.add_argument("--aug_seed", type=int, default=None, help="augmentation: seed of the device generator (default 0; rank r uses seed + r)")
     return p
+
+
+AUGMENT_FLAGS = ("aug_brightness", "aug_contrast", "aug_saturation", "aug_noise_std", "aug_erase_prob", "aug_erase_scale", "aug_erase_fill", "aug_seed")
+
+
+def build_augment(args, rank=0):
+    """the --aug_* family -> util.data_utils.FrameAugment, or None when none of its flags is given.  The flags need --episodes: the
+    synthetic episodes are preprocessed float images, which the augmentation does not take."""
+    from rgb_proprioceptive_pose_estimator_amd.util.data_utils import FrameAugment
+    given = {k: getattr(args, k, None) for k in AUGMENT_FLAGS}
+    if all(v is None for v in given.values()) and not getattr(args, "aug_per_frame", False):
+        return None
+    if not getattr(args, "episodes", None):
+        raise SystemExit("the --aug_* flags need --episodes: the augmentation works on recorded raw uint8 frames")
+    fill = given["aug_erase_fill"] or "mean"
+    if fill not in ("mean", "noise"):
+        try:
+            fill = tuple(int(v) for v in fill.split(","))
+        except ValueError:
+            raise SystemExit("--aug_erase_fill is 'mean', 'noise' or R,G,B; got %r" % given["aug_erase_fill"])
+    try:
+        return FrameAugment(brightness=given["aug_brightness"] or 0.0, contrast=given["aug_contrast"] or 0.0, saturation=given["aug_saturation"] or 0.0,
+                            noise_std=given["aug_noise_std"] or 0.0, erase_prob=given["aug_erase_prob"] or 0.0,
+                            erase_scale=tuple(given["aug_erase_scale"] or (0.1, 0.3)), erase_fill=fill, per_episode=not args.aug_per_frame,
+                            seed=(given["aug_seed"] or 0) + rank)
+    except ValueError as e:
+        raise SystemExit("--aug_*: %s" % e)
 
 
 DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
@@ -162,6 +202,7 @@ def build_optimizer(args, params):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    build_augment(args)   # (a flag that cannot be honoured stops the run before anything is built)
     from rgb_proprioceptive_pose_estimator_amd.dist import init_from_env
     from rgb_proprioceptive_pose_estimator_amd.models import PoseDistanceLoss
     from rgb_proprioceptive_pose_estimator_amd.util.data_utils import RecordedEpisodeDataset, SyntheticEpisodeDataset
@@ -200,7 +241,7 @@ def main(argv=None):
         print("Training...")
     return train(model=model, dataset=dataset, criterion=criterion, optimizer=optimizer, num_epochs=args.n_epochs,
                  num_train_episodes_per_epoch=args.n_train_episodes_per_epoch, num_val_episodes_per_epoch=args.n_val_episodes_per_epoch,
-                 params=params, device=device, save_model=not args.no_save)
+                 params=params, device=device, save_model=not args.no_save, augment=build_augment(args, rank))
 
 
 if __name__ == "__main__":

@@ -16,6 +16,7 @@ ResNet; models/losses.py:114-128 is the loss; util/learn_utils.py:152-184 the st
     rpe::pose_loss / pose_distance_loss             PoseDistanceLoss (raw three-value form / differentiable scalar)
     rpe::pose_errors                                its "val" branch per sample: position error, |angle| error, unit-quaternion pose
     rpe::adam_step                                  torch.optim.Adam's update of one flat fp32 tensor, in place
+    rpe::augment_frames_u8                          (no counterpart: the reference does not augment) jitter, noise and erasing of raw uint8 frames
 
 Importing this module needs torch only; the HIP library is loaded on the first call (ops.py), so the schemas can be inspected on a
 machine without a GPU (tests/test_host_cpu.py).
@@ -27,7 +28,7 @@ import torch
 __all__ = ["NAMES"]
 
 _NS = "rpe"
-NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step")
+NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step", "augment_frames_u8")
 
 
 def _ops():
@@ -179,3 +180,19 @@ def _(pred, truth, eps):
 @torch.library.custom_op(_NS + "::adam_step", mutates_args=("p", "m", "v"), device_types="cuda")
 def adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr: float, beta1: float, beta2: float, eps: float, step: int) -> None:
     _ops().adam_step(p, g, m, v, lr, beta1, beta2, eps, step)
+
+
+# ---- frame augmentation --------------------------------------------------------------------------------------------------------
+@torch.library.custom_op(_NS + "::augment_frames_u8", mutates_args=("state",), device_types="cuda")
+def augment_frames_u8(frames: torch.Tensor, desc: List[int], state: torch.Tensor) -> torch.Tensor:
+    """frames uint8 (..., Hs, Ws, 3) -> augmented uint8 frames; desc: the integers of rpe_augment_desc in the order of
+    ops.AUGMENT_DESC_FIELDS; state: int32, element 0 is the step counter, advanced by one"""
+    ops = _ops()
+    if len(desc) != len(ops.AUGMENT_DESC_FIELDS):
+        raise ValueError("augment_frames_u8: desc has %d integers (%s)" % (len(ops.AUGMENT_DESC_FIELDS), ", ".join(ops.AUGMENT_DESC_FIELDS)))
+    return ops.augment_frames_u8(frames, ops.augment_desc(**dict(zip(ops.AUGMENT_DESC_FIELDS, desc))), state)
+
+
+@augment_frames_u8.register_fake
+def _(frames, desc, state):
+    return torch.empty_like(frames)

@@ -126,6 +126,8 @@ def synthetic_batch(lead, seed, hw=224, with_depth=False, noise_scale=0.001, dev
 class SyntheticEpisodeDataset(Dataset):
     """MultiEpisodeDataset-shaped source of seeded synthetic episodes, resident on `device`."""
 
+    frame_dtype = torch.float32   # preprocessed (normalised) images: nothing for FrameAugment to work on
+
     def __init__(self, horizon=20, use_depth=False, obj_name=None, is_two_arm=False, motion="random", seed=1234, hw=224,
                  device="cuda", env_name="Synthetic"):
         if motion not in MOTIONS:
@@ -189,6 +191,7 @@ class RecordedEpisodeDataset(Dataset):
     file order, wrapping around, and draws fresh measurement noise (util/data_utils.py:162-167)."""
 
     _POSES = ("true_self", "true_other", "true_obj")
+    frame_dtype = torch.uint8
 
     def __init__(self, path, use_depth=False, obj_name=None, seed=1234):
         import numpy as np
@@ -270,6 +273,137 @@ class RecordedEpisodeDataset(Dataset):
         x0bar = x0 + (noise_scale ** 0.5) * torch.randn(x0.shape, generator=self._gen)
         data["measurement_self"] = torch.cat([x0bar[..., :3], x0bar[..., 3:] / x0bar[..., 3:].norm(dim=-1, keepdim=True)], dim=-1)
         self.data = data
+
+
+NOISE_SUM_STD = 147.8005   # standard deviation of the sum of four uniform bytes: sqrt(4 (256^2 - 1) / 12)
+ERASE_FILL_MEAN = (124, 116, 104)   # the ImageNet mean in bytes: normalises to ~0
+
+
+def _q16(f):
+    return int(round(65536.0 * f))
+
+
+def _jitter_range(name, amount):
+    """torchvision's ColorJitter range for a non-negative amount: factors in [max(0, 1 - a), 1 + a], as Q16 integers"""
+    a = float(amount)
+    if not 0.0 <= a <= 3.0:
+        raise ValueError("{} must lie in [0, 3] (factors up to 4); got {!r}".format(name, amount))
+    return _q16(max(0.0, 1.0 - a)), _q16(1.0 + a)
+
+
+class FrameAugment:
+    """Label-preserving augmentation of raw uint8 camera frames on the device (rpe_augment_frames_u8; DESIGN.md "Frame
+    augmentation"): brightness / contrast / saturation jitter with torchvision's ranges (`brightness=b`: a factor in
+    [max(0, 1 - b), 1 + b]), sensor noise of `noise_std` grey levels, and random erasing of one rectangle per frame with probability
+    `erase_prob`, each side a fraction `erase_scale` = (lo, hi) of the frame's, filled with `erase_fill`: "mean" (the ImageNet mean,
+    which normalises to ~0), "noise" (random bytes) or an (r, g, b) tuple.  No crop, shift or flip: the labels are absolute poses
+    seen by a fixed camera.  The random numbers are drawn on the device from (seed, step); the step counter lives in device memory
+    and every call advances it, also a call replayed from a captured graph.
+    per_episode: frames (S, N, Hs, Ws, 3) share their jitter and occluder along S (one episode keeps them through the chunk); the
+    noise is always per frame.  A 4-D batch (B, Hs, Ws, 3) draws per frame.
+
+        aug = FrameAugment(brightness=0.2, contrast=0.2, noise_std=2.0, erase_prob=0.25)
+        frames = aug(frames)                # uint8 device frames -> a new uint8 tensor of the same shape
+    """
+
+    def __init__(self, brightness=0., contrast=0., saturation=0., noise_std=0., erase_prob=0., erase_scale=(0.1, 0.3), erase_fill="mean",
+                 per_episode=True, seed=0):
+        self.qb = _jitter_range("brightness", brightness)
+        self.qc = _jitter_range("contrast", contrast)
+        self.qs = _jitter_range("saturation", saturation)
+        if not float(noise_std) >= 0.0:
+            raise ValueError("noise_std must not be negative; got {!r}".format(noise_std))
+        self.noise_q = _q16(float(noise_std) / NOISE_SUM_STD)
+        if self.noise_q > 4 * 65536:
+            raise ValueError("noise_std {!r} is beyond the kernel's range ({:.0f} grey levels)".format(noise_std, 4 * NOISE_SUM_STD))
+        if not 0.0 <= float(erase_prob) <= 1.0:
+            raise ValueError("erase_prob must lie in [0, 1]; got {!r}".format(erase_prob))
+        self.erase_thresh = min(2 ** 32 - 1, int(round(float(erase_prob) * 2 ** 32)))
+        lo, hi = (float(v) for v in erase_scale)
+        if not 0.0 < lo <= hi <= 1.0:
+            raise ValueError("erase_scale must be (lo, hi) with 0 < lo <= hi <= 1; got {!r}".format(erase_scale))
+        self.erase_scale = (lo, hi)
+        if erase_fill == "mean":
+            self.fill_mode, self.fill_rgb = 0, ERASE_FILL_MEAN
+        elif erase_fill == "noise":
+            self.fill_mode, self.fill_rgb = 1, ERASE_FILL_MEAN
+        else:
+            try:
+                rgb = tuple(int(v) for v in erase_fill)
+            except (TypeError, ValueError):
+                rgb = ()
+            if len(rgb) != 3 or not all(0 <= v <= 255 for v in rgb):
+                raise ValueError('erase_fill is "mean", "noise" or an (r, g, b) tuple of bytes; got {!r}'.format(erase_fill))
+            self.fill_mode, self.fill_rgb = 0, rgb
+        self.per_episode = bool(per_episode)
+        self.seed = int(seed)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must fit 64 unsigned bits; got {!r}".format(seed))
+        self.last_params = None     # device table of the last call: [0] the step used, then per stream qb qc qs erase top left h w
+        self._state = None          # int32 device tensor, element 0 = the step counter
+        self._step0 = 0             # the counter while there is no device tensor yet
+        self._buffers = {}
+
+    def erase_bounds(self, size):
+        """erase_scale as pixel bounds (lo, hi) of a side of `size` pixels, 1 <= lo <= hi <= size"""
+        lo = min(size, max(1, int(round(self.erase_scale[0] * size))))
+        return lo, min(size, max(lo, int(round(self.erase_scale[1] * size))))
+
+    def desc_fields(self, hs, ws, group=0):
+        """the integers of rpe_augment_desc for frames of hs x ws"""
+        (eh_lo, eh_hi), (ew_lo, ew_hi) = self.erase_bounds(hs), self.erase_bounds(ws)
+        return dict(seed=self.seed, qb_lo=self.qb[0], qb_hi=self.qb[1], qc_lo=self.qc[0], qc_hi=self.qc[1], qs_lo=self.qs[0], qs_hi=self.qs[1],
+                    noise_q=self.noise_q, erase_thresh=self.erase_thresh, eh_lo=eh_lo, eh_hi=eh_hi, ew_lo=ew_lo, ew_hi=ew_hi, fill_mode=self.fill_mode,
+                    fill_r=self.fill_rgb[0], fill_g=self.fill_rgb[1], fill_b=self.fill_rgb[2], group=int(group))
+
+    @staticmethod
+    def check_frames(frames):
+        """ValueError unless `frames` are uint8 device frames, channels last: (B, Hs, Ws, 3) or (S, N, Hs, Ws, 3), contiguous"""
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8:
+            raise ValueError("FrameAugment takes raw uint8 frames; got {}".format(getattr(frames, "dtype", type(frames))))
+        if frames.dim() not in (4, 5) or frames.shape[-1] != 3 or not frames.is_contiguous() or frames.numel() == 0:
+            raise ValueError("FrameAugment takes channels-last frames (B, Hs, Ws, 3) or (S, N, Hs, Ws, 3), contiguous; got {}".format(tuple(frames.shape)))
+        if not frames.is_cuda:
+            raise ValueError("FrameAugment runs on the device only (there is no CPU path); got a {} tensor".format(frames.device))
+
+    def _device_state(self, device):
+        if self._state is None or self._state.device != device:
+            step = self.step
+            self._state = torch.tensor([step - (1 << 32) if step >= (1 << 31) else step], dtype=torch.int32, device=device)
+        return self._state
+
+    def __call__(self, frames, out=None):
+        from .. import ops
+        self.check_frames(frames)
+        hs, ws = frames.shape[-3:-1]
+        group = frames.shape[1] if self.per_episode and frames.dim() == 5 else 0
+        b = frames.numel() // (hs * ws * 3)
+        state = self._device_state(frames.device)
+        key = (b, group, frames.device)
+        if key not in self._buffers:   # kept: a captured call has their addresses
+            self._buffers[key] = (torch.empty(1 + 8 * (group or b), dtype=torch.int32, device=frames.device),
+                                  torch.empty(b, dtype=torch.int64, device=frames.device))
+        params, sums = self._buffers[key]
+        out = ops.augment_frames_u8(frames, ops.augment_desc(**self.desc_fields(hs, ws, group)), state, out=out, params=params, sums=sums)
+        self.last_params = params
+        return out
+
+    @property
+    def step(self):
+        """the step counter: the number of calls so far, replays of a captured call included (reads the device)"""
+        return self._step0 if self._state is None else int(self._state[0].item()) & 0xFFFFFFFF
+
+    def state_dict(self):
+        return {"seed": self.seed, "step": self.step}
+
+    def load_state_dict(self, sd):
+        seed, step = int(sd["seed"]), int(sd["step"])
+        if not (0 <= seed < 2 ** 64 and 0 <= step < 2 ** 32):
+            raise ValueError("FrameAugment.load_state_dict: seed / step out of range: {!r}".format(sd))
+        self.seed = seed
+        self._step0 = step
+        if self._state is not None:   # in place: a captured call keeps reading this tensor
+            self._state.fill_(step - (1 << 32) if step >= (1 << 31) else step)
 
 
 class FramePrefetcher:

@@ -114,24 +114,38 @@ class GraphedTrainStep:
         loss, pos_err, ori_err = step(batch)          # device scalars, valid until the next call
     """
 
-    def __init__(self, model, criterion, optimizer, train_obj_pose, example_batch, warmup=3):
+    def __init__(self, model, criterion, optimizer, train_obj_pose, example_batch, warmup=3, augment=None):
         if dist.is_initialized() and dist.get_world_size() > 1:
             raise RuntimeError("GraphedTrainStep is single-process; data-parallel steps run eagerly")
         if not getattr(optimizer, "capturable", False):
             raise RuntimeError("GraphedTrainStep needs FusedAdam(..., capturable=True): the step count must live on the device")
         self.model, self.criterion, self.optimizer, self.train_obj_pose = model, criterion, optimizer, train_obj_pose
         self.static = tuple(None if t is None else t.clone() for t in example_batch)
+        # augment (util.data_utils.FrameAugment): the augmentation is part of the captured step -- it reads the static raw frames and
+        # writes a buffer of its own, which is what the model is fed.  Its step counter lives on the device and the captured launch
+        # advances it, so every replay draws fresh parameters (the warm-up steps below advance it as well).
+        self.augment = augment
+        self.fed = self.static
+        if augment is not None:
+            augment.check_frames(self.static[0])
+            self.fed = (torch.empty_like(self.static[0]),) + self.static[1:]
+
+        def step():
+            if augment is not None:
+                augment(self.static[0], out=self.fed[0])
+            return train_step(model, self.fed, criterion, optimizer, train_obj_pose, "train", None)
+
         model.train()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):   # warm-up on a side stream: plans, workspaces and scratch buffers exist before the capture
             for _ in range(warmup):
-                train_step(model, self.static, criterion, optimizer, train_obj_pose, "train", None)
+                step()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
-            self.out = train_step(model, self.static, criterion, optimizer, train_obj_pose, "train", None)
+            self.out = step()
         self.warmup_steps = warmup   # optimizer steps taken while building (the capture itself does not execute anything)
         self._keep = _graph_keepalive(model)
 
@@ -379,7 +393,7 @@ def evaluate_episodes(model, dataset, num_episodes, params, *, max_frames=256, n
 
 
 def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_per_epoch, num_val_episodes_per_epoch, params, device,
-          save_path='default', save_model=True, logging=True, *, save_optimizer=False):
+          save_path='default', save_model=True, logging=True, *, save_optimizer=False, augment=None):
     """See the module docstring.  Returns (model with the best validation weights, best validation loss).
     save_optimizer (addition; the reference saves weights only): also write `<save_path>.optim` with the optimizer state of the
     best-validation epoch so that a run can be resumed (`optimizer.load_state_dict(torch.load(path))`).
@@ -387,7 +401,13 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
     validation loss is theirs, and beside `<save_path>` (the raw weights, unchanged: a resume with `.optim` continues exactly)
     `<save_path>.ema` holds model.state_dict() with the averaged weights -- reference-shaped, so scripts/rollout.py
     --checkpoint_model_path X.ema loads it as it is.  BatchNorm's running statistics are not averaged: `.ema` carries those of the
-    raw run.  With a schedule (lr_schedule=...) the per-epoch train line shows the current rate of the first param group."""
+    raw run.  With a schedule (lr_schedule=...) the per-epoch train line shows the current rate of the first param group.
+    augment (util.data_utils.FrameAugment): applied on the device to the raw uint8 frames of the `train` phase, between their staging
+    copy and the model; the `val` phase sees the recorded pixels.  Needs a dataset of raw frames (RecordedEpisodeDataset): with
+    preprocessed float images it is a ValueError."""
+    if augment is not None and getattr(dataset, "frame_dtype", torch.uint8) != torch.uint8:
+        raise ValueError("train(augment=...) needs raw uint8 frames (RecordedEpisodeDataset); {} hands out {} images".format(
+            type(dataset).__name__, dataset.frame_dtype))
     train_obj_pose = hasattr(model, "object_name")
     dt_string = datetime.now().strftime("%d-%m-%Y_%H-%M-%S")
     since = time.time()
@@ -435,6 +455,10 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
                         depth = None if depth is None else depth[0]
                         x1 = None if x1 is None else x1[0]
                         obj = None if obj is None else obj[0]
+                    if augment is not None and phase == "train":
+                        if img.dtype != torch.uint8:
+                            raise ValueError("train(augment=...) needs raw uint8 frames; the dataset hands out {} images".format(img.dtype))
+                        img = augment(img)
                     loss, pe, oe = train_step(model, (img, depth, x0bar, x0, x1, obj), criterion, optimizer, train_obj_pose, phase, grad_sync)
                     sums += torch.stack([loss.double(), pe.double(), oe.double()])
                     if clip_sums is not None:
