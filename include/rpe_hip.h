@@ -269,6 +269,29 @@ typedef struct {
 int rpe_augment_frames_u8(const unsigned char* in, unsigned char* out, int B, int Hs, int Ws, const rpe_augment_desc* d, unsigned* state, int* params,
                           unsigned long long* sums, void* stream);
 
+/* Shuffled minibatches from recorded episodes resident in device memory (no counterpart in the reference, whose DataLoader walks the
+ * episodes in lockstep, unshuffled): an index launch and a row gather in front of rpe_augment_frames_u8 / rpe_stage_frames_u8[_resized].
+ * All arithmetic is unsigned / 64-bit integer and specified to the bit ("Minibatch sampling").
+ * Windows: K = (T - S) / stride + 1 start positions per episode, M = E K windows over the E selected episodes; window w is episode
+ * sel[w / K], first timestep (w % K) * stride.  Draw i of step `step` has the global index g = step N + i (64 bits), epoch = g / M,
+ * pos = g % M; shuffle 0: w = pos; shuffle 1: w = the epoch's keyed bijection of [0, M) at pos (4-round balanced Feistel network on
+ * Philox4x32-10 keyed by `seed`, counter (R, round, epoch mod 2^32, 0x53414D50), cycle-walked), so M consecutive draws from a multiple
+ * of M visit every window once. */
+typedef struct {
+    unsigned long long seed;
+    int E, T, S, stride, N; /* selected episodes, timesteps per episode, timesteps per window, distance of window starts, windows per step */
+    int shuffle;            /* 0: file order, 1: a fresh keyed permutation per epoch */
+} rpe_sample_desc;
+/* sel: device, E episode numbers in the file.  state: device, state[0] is the step counter -- the launch reads it and advances it by
+ * one, so a captured call draws the next batch at every replay.  index: device, 1 + 2 N ints, receives [0] = the step used, then per
+ * window (episode number in the file, first timestep).  E K must stay below 2^31.  One launch of one workgroup. */
+int rpe_sample_windows(const rpe_sample_desc* d, const int* sel, unsigned* state, int* index, void* stream);
+/* out row s N + n <- pool row index.episode[n] * T + index.t0[n] + s for s < S, n < N; rows of row_bytes bytes, 64-bit offsets.  pool:
+ * device, [episodes in the file][T] rows; out: device, [S][N] rows, not overlapping the pool; index: as rpe_sample_windows writes it
+ * (the entries are trusted: episode < episodes in the file, t0 + S <= T).  16-byte loads and stores when row_bytes and both pointers
+ * are multiples of 16, 4-byte when multiples of 4, single bytes otherwise.  One launch. */
+int rpe_gather_rows(const void* pool, void* out, long row_bytes, long T, const int* index, int S, int N, void* stream);
+
 /* ------------------------------------------------------------------ batch norm */
 /* replaces: nn.BatchNorm2d (train mode: biased batch variance, eps, momentum with
  * unbiased running variance) + the in-place nn.ReLU and `out += identity` of the

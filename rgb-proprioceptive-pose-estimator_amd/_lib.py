@@ -43,6 +43,11 @@ class AugmentDesc(Structure):
                 + [("fill_rgb", ctypes.c_ubyte * 3), ("group", c_int)])
 
 
+class SampleDesc(Structure):
+    """rpe_sample_desc"""
+    _fields_ = [("seed", ctypes.c_ulonglong)] + [(n, c_int) for n in ("E", "T", "S", "stride", "N", "shuffle")]
+
+
 P, I, L, F, D = c_void_p, c_int, c_long, c_float, c_double
 PD = POINTER(ConvDesc)
 
@@ -92,6 +97,8 @@ _SPEC = {
     "rpe_stage_frames_u8_resized": (I, [I, P, P, I, I, I, I, I, I, I, I, I, P, P, I, P, P, I, P, POINTER(c_float), POINTER(c_float), P]),
     "rpe_stage_depth_f32_resized": (I, [P, P, I, I, I, I, I, I, I, I, I, P, P, I, P, P, I, P]),
     "rpe_augment_frames_u8": (I, [P, P, I, I, I, POINTER(AugmentDesc), P, P, P, P]),
+    "rpe_sample_windows": (I, [POINTER(SampleDesc), P, P, P, P]),
+    "rpe_gather_rows": (I, [P, P, L, L, P, I, I, P]),
     "rpe_bn_finalize": (I, [P, I, I, L, P, P, P, P, P, F, F, P, P, P, P, P, P]),
     "rpe_bn_eval_affine": (I, [I, P, P, P, P, F, P, P, P]),
     "rpe_bn_apply": (I, [I, P, P, P, P, P, L, I, I, P]),

@@ -19,17 +19,6 @@ namespace rpe {
 typedef unsigned long long u64;
 static_assert(sizeof(rpe_augment_desc) == 72, "rpe_augment_desc: _lib.AugmentDesc mirrors this layout");
 
-__device__ inline void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned r[4]) {
-#pragma unroll
-    for (int i = 0; i < 10; ++i) {
-        if (i) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
-        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-    }
-    r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
-
 // bounded draw over n values: (r * n) >> 32
 __device__ inline int draw(unsigned r, unsigned n) { return (int)__umulhi(r, n); }
 

@@ -136,6 +136,19 @@ __device__ inline double wave_sum_d(double v) {
     return v;
 }
 
+// ---- Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3"): counter (c0..c3), key (k0, k1) -> four words.
+// The generator of the frame augmentation (augment.hip) and of the window sampler (sample.hip); tests/_augment_oracle.py restates it.
+__device__ inline void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned r[4]) {
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        if (i) { k0 += 0x9E3779B9u; k1 += 0xBB67AE85u; }
+        const unsigned h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
+        const unsigned h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
+        c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
+    }
+    r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+
 inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
 // ---- walk direction ("boustrophedon") -----------------------------------------------------------------------------

@@ -758,3 +758,57 @@ def augment_frames_u8(frames, desc, state, out=None, params=None, sums=None):
         raise ValueError("augment_frames_u8: sums must be int64 with at least %d elements" % b)
     lib.rpe_augment_frames_u8(_p(frames), _p(out), b, hs, ws, ctypes.byref(desc), _p(state), _p(_chk(params, "params")), _p(_chk(sums, "sums")), _stream())
     return out
+
+
+SAMPLE_DESC_FIELDS = ("seed", "E", "T", "S", "stride", "N", "shuffle")
+
+
+def sample_desc(seed=0, E=1, T=1, S=1, stride=1, N=1, shuffle=1):
+    """rpe_sample_desc from plain integers; SAMPLE_DESC_FIELDS is the order of the flat list form `torch.ops.rpe.sample_windows` takes"""
+    from ._lib import SampleDesc
+    d = SampleDesc()
+    d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    for k, v in (("E", E), ("T", T), ("S", S), ("stride", stride), ("N", N), ("shuffle", shuffle)):
+        setattr(d, k, int(v))
+    return d
+
+
+def sample_windows(desc, sel, state, out=None):
+    """-> index, int32 (1 + 2 N,): [0] the step used, then per window (episode number in the file, first timestep)
+    (rpe_sample_windows).  desc: sample_desc(...).  sel: int32 device tensor, the file's episode numbers of the desc.E selected
+    episodes.  state: int32 device tensor whose element 0 is the step counter; the launch advances it by one."""
+    dev = sel.device
+    if sel.dtype != torch.int32 or sel.dim() != 1 or sel.numel() < desc.E:
+        raise ValueError("sample_windows: sel must be an int32 vector of at least E = %d episode numbers" % desc.E)
+    if state.dtype != torch.int32 or state.numel() < 1 or state.device != dev:
+        raise ValueError("sample_windows: state must be an int32 tensor on sel's device")
+    n = 1 + 2 * max(int(desc.N), 0)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or out.numel() < n or out.device != dev:
+        raise ValueError("sample_windows: out must be int32 with at least %d elements on sel's device" % n)
+    lib.rpe_sample_windows(ctypes.byref(desc), _p(_chk(sel, "sel")), _p(_chk(state, "state")), _p(_chk(out, "out")), _stream())
+    return out
+
+
+def gather_rows(pool, index, S, T, out=None):
+    """pool (E_file, T, ...) contiguous, any dtype -> (S, N, ...) of that dtype: out[s, n] = pool[index.episode[n], index.t0[n] + s]
+    (rpe_gather_rows).  index: int32 (1 + 2 N,) as sample_windows writes it; its entries are trusted (episode < E_file,
+    t0 + S <= T).  out: destination, contiguous (a captured call keeps its address)."""
+    if pool.dim() < 2 or pool.shape[1] != T or pool.numel() == 0:
+        raise ValueError("gather_rows: pool must be (E_file, T = %d, ...); got %r" % (T, tuple(pool.shape)))
+    _chk(pool, "pool")
+    dev = pool.device
+    if index.dtype != torch.int32 or index.dim() != 1 or index.numel() < 3 or index.numel() % 2 != 1 or index.device != dev:
+        raise ValueError("gather_rows: index must be an int32 vector of 1 + 2 N elements on the pool's device")
+    n = (index.numel() - 1) // 2
+    if not 1 <= int(S) <= T:
+        raise ValueError("gather_rows: S must lie in [1, T = %d]; got %r" % (T, S))
+    shape = (int(S), n) + tuple(pool.shape[2:])
+    if out is None:
+        out = torch.empty(shape, dtype=pool.dtype, device=dev)
+    elif out.dtype != pool.dtype or tuple(out.shape) != shape or out.device != dev:
+        raise ValueError("gather_rows: out must be %s %r on the pool's device" % (pool.dtype, shape))
+    row_bytes = pool[0, 0].numel() * pool.element_size()
+    lib.rpe_gather_rows(_p(pool), _p(_chk(out, "out")), row_bytes, int(T), _p(_chk(index, "index")), int(S), n, _stream())
+    return out

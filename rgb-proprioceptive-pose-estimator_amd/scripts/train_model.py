@@ -9,7 +9,9 @@ Added flags: --dtype {bf16,f16,f32}, --optimizer {fused,torch}, --max_grad_norm,
 learning-rate schedule (--lr_schedule, --warmup_steps, --warmup_start_factor, --lr_total_steps, --lr_min_factor, --lr_step_size,
 --lr_gamma), --trunk_lr_scale (the trunk as a param group of its own) and --ema_decay (writes `<checkpoint>.ema` beside the raw weights);
 the on-device frame augmentation of recorded episodes (--aug_brightness, --aug_contrast, --aug_saturation, --aug_noise_std,
---aug_erase_prob, --aug_erase_scale, --aug_erase_fill, --aug_per_frame, --aug_seed; all off by default, they need --episodes).
+--aug_erase_prob, --aug_erase_scale, --aug_erase_fill, --aug_per_frame, --aug_seed; all off by default, they need --episodes);
+--resident (the --episodes file lives in HBM) and, with it, --batch_size, --window_stride, --shuffle_seed (shuffled minibatches drawn on the
+device instead of one chunk of every episode per step).
 
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 scripts/train_model.py ...`;
 episodes are sharded over ranks and gradients SUM-all-reduced over RCCL.
@@ -92,7 +94,38 @@ def build_parser():
     p.add_argument("--aug_per_frame", action="store_true",
                    help="augmentation: draw jitter and occluder per frame (default: per episode, kept through a chunk of --sequence_length steps)")
     p.add_argument("--aug_seed", type=int, default=None, help="augmentation: seed of the device generator (default 0; rank r uses seed + r)")
+    p.add_argument("--resident", action="store_true",
+                   help="keep the whole --episodes file in HBM (util.data_utils.ResidentEpisodeDataset): batches are gathered on the device, no PCIe per step")
+    p.add_argument("--batch_size", type=int, default=None,
+                   help="train on shuffled minibatches of this many windows of --sequence_length steps (one frame for the models without a sequence), "
+                        "drawn on the device (needs --episodes --resident; default: one chunk of every episode per step, in file order)")
+    p.add_argument("--window_stride", type=int, default=None, help="sampling: distance of window starts (default: the window's length; 1 = every offset)")
+    p.add_argument("--shuffle_seed", type=int, default=None, help="sampling: seed of the device sampler (default 0; rank r uses seed + r)")
     return p
+
+
+def build_sampling(args):
+    """--resident / --batch_size / --window_stride / --shuffle_seed -> the keyword arguments of train() that select minibatch
+    sampling ({} when --batch_size is not given).  --resident needs --episodes, the other three need --episodes --resident."""
+    if getattr(args, "resident", False) and not getattr(args, "episodes", None):
+        raise SystemExit("--resident needs --episodes: it keeps a file of recorded episodes in HBM")
+    batch_size = getattr(args, "batch_size", None)
+    for flag in ("batch_size", "window_stride", "shuffle_seed"):
+        if getattr(args, flag, None) is not None and not (getattr(args, "episodes", None) and getattr(args, "resident", False)):
+            raise SystemExit("--%s needs --episodes --resident: minibatches are drawn on the device from episodes resident in HBM" % flag)
+    if batch_size is None:
+        for flag in ("window_stride", "shuffle_seed"):
+            if getattr(args, flag, None) is not None:
+                raise SystemExit("--%s needs --batch_size" % flag)
+        return {}
+    if batch_size < 1:
+        raise SystemExit("--batch_size must be at least 1; got %d" % batch_size)
+    if args.window_stride is not None and args.window_stride < 1:
+        raise SystemExit("--window_stride must be at least 1; got %d" % args.window_stride)
+    seed = args.shuffle_seed or 0
+    if not 0 <= seed < 2 ** 64:
+        raise SystemExit("--shuffle_seed must fit 64 unsigned bits; got %d" % seed)
+    return dict(batch_size=batch_size, window_stride=args.window_stride, shuffle_seed=seed)
 
 
 AUGMENT_FLAGS = ("aug_brightness", "aug_contrast", "aug_saturation", "aug_noise_std", "aug_erase_prob", "aug_erase_scale", "aug_erase_fill", "aug_seed")
@@ -203,9 +236,10 @@ def build_optimizer(args, params):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     build_augment(args)   # (a flag that cannot be honoured stops the run before anything is built)
+    sampling = build_sampling(args)
     from rgb_proprioceptive_pose_estimator_amd.dist import init_from_env
     from rgb_proprioceptive_pose_estimator_amd.models import PoseDistanceLoss
-    from rgb_proprioceptive_pose_estimator_amd.util.data_utils import RecordedEpisodeDataset, SyntheticEpisodeDataset
+    from rgb_proprioceptive_pose_estimator_amd.util.data_utils import RecordedEpisodeDataset, ResidentEpisodeDataset, SyntheticEpisodeDataset
     from rgb_proprioceptive_pose_estimator_amd.util.learn_utils import train
     from rgb_proprioceptive_pose_estimator_amd.util.model_utils import lr_param_groups
 
@@ -229,7 +263,8 @@ def main(argv=None):
         model.load_state_dict(torch.load(args.checkpoint_model_path, map_location="cpu"))
     optimizer = build_optimizer(args, lr_param_groups(model, args.trunk_lr_scale))
     if args.episodes:
-        dataset = RecordedEpisodeDataset(args.episodes, use_depth=args.use_depth, obj_name=args.obj_name, seed=args.episodes_seed + 1000 * rank)
+        kw = dict(use_depth=args.use_depth, obj_name=args.obj_name, seed=args.episodes_seed + 1000 * rank)
+        dataset = ResidentEpisodeDataset(args.episodes, device=device, **kw) if args.resident else RecordedEpisodeDataset(args.episodes, **kw)
         if args.horizon != build_parser().get_default("horizon") and args.horizon != dataset.env.horizon and rank == 0:
             warnings.warn("--horizon {} ignored: the episodes of {} have {} steps".format(args.horizon, args.episodes, dataset.env.horizon))
         args.horizon = dataset.env.horizon
@@ -241,7 +276,7 @@ def main(argv=None):
         print("Training...")
     return train(model=model, dataset=dataset, criterion=criterion, optimizer=optimizer, num_epochs=args.n_epochs,
                  num_train_episodes_per_epoch=args.n_train_episodes_per_epoch, num_val_episodes_per_epoch=args.n_val_episodes_per_epoch,
-                 params=params, device=device, save_model=not args.no_save, augment=build_augment(args, rank))
+                 params=params, device=device, save_model=not args.no_save, augment=build_augment(args, rank), **sampling)
 
 
 if __name__ == "__main__":

@@ -17,6 +17,7 @@ ResNet; models/losses.py:114-128 is the loss; util/learn_utils.py:152-184 the st
     rpe::pose_errors                                its "val" branch per sample: position error, |angle| error, unit-quaternion pose
     rpe::adam_step                                  torch.optim.Adam's update of one flat fp32 tensor, in place
     rpe::augment_frames_u8                          (no counterpart: the reference does not augment) jitter, noise and erasing of raw uint8 frames
+    rpe::sample_windows / gather_rows               DataLoader(shuffle=True) over episode windows resident in HBM: the batch's index, and its rows
 
 Importing this module needs torch only; the HIP library is loaded on the first call (ops.py), so the schemas can be inspected on a
 machine without a GPU (tests/test_host_cpu.py).
@@ -28,7 +29,7 @@ import torch
 __all__ = ["NAMES"]
 
 _NS = "rpe"
-NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step", "augment_frames_u8")
+NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step", "augment_frames_u8", "sample_windows", "gather_rows")
 
 
 def _ops():
@@ -196,3 +197,31 @@ def augment_frames_u8(frames: torch.Tensor, desc: List[int], state: torch.Tensor
 @augment_frames_u8.register_fake
 def _(frames, desc, state):
     return torch.empty_like(frames)
+
+
+# ---- minibatch sampling from resident episodes ---------------------------------------------------------------------------------
+@torch.library.custom_op(_NS + "::sample_windows", mutates_args=("state",), device_types="cuda")
+def sample_windows(desc: List[int], sel: torch.Tensor, state: torch.Tensor) -> torch.Tensor:
+    """-> int32 (1 + 2 N,): the step used, then per window (episode number in the file, first timestep); desc: the integers of
+    rpe_sample_desc in the order of ops.SAMPLE_DESC_FIELDS; sel: int32 episode numbers; state: int32, element 0 is the step
+    counter, advanced by one"""
+    ops = _ops()
+    if len(desc) != len(ops.SAMPLE_DESC_FIELDS):
+        raise ValueError("sample_windows: desc has %d integers (%s)" % (len(ops.SAMPLE_DESC_FIELDS), ", ".join(ops.SAMPLE_DESC_FIELDS)))
+    return ops.sample_windows(ops.sample_desc(**dict(zip(ops.SAMPLE_DESC_FIELDS, desc))), sel, state)
+
+
+@sample_windows.register_fake
+def _(desc, sel, state):
+    return sel.new_empty((1 + 2 * desc[5],))
+
+
+@torch.library.custom_op(_NS + "::gather_rows", mutates_args=(), device_types="cuda")
+def gather_rows(pool: torch.Tensor, index: torch.Tensor, S: int, T: int) -> torch.Tensor:
+    """pool (E_file, T, ...) -> (S, N, ...): out[s, n] = pool[index.episode[n], index.t0[n] + s], index as rpe::sample_windows writes it"""
+    return _ops().gather_rows(pool, index, S, T)
+
+
+@gather_rows.register_fake
+def _(pool, index, S, T):
+    return pool.new_empty((S, (index.shape[0] - 1) // 2) + tuple(pool.shape[2:]))

@@ -8,7 +8,8 @@ episodes at timestep t, util/data_utils.py:62-73), the 6-tuple, `refresh_data`, 
 (ImageNet-normalised uint8 noise images, workspace-bounded positions, unit quaternions with w >= 0,
 proprioception = truth + N(0, noise_scale I) with the quaternion renormalised, util/data_utils.py:162-176),
 generated directly in HBM.  RecordedEpisodeDataset reads episodes recorded from the simulator elsewhere back from a file, raw, and
-leaves every image transform to the device.
+leaves every image transform to the device; ResidentEpisodeDataset keeps that file in HBM and WindowSampler draws shuffled minibatches
+from it on the device.
 """
 import types
 
@@ -273,6 +274,171 @@ class RecordedEpisodeDataset(Dataset):
         x0bar = x0 + (noise_scale ** 0.5) * torch.randn(x0.shape, generator=self._gen)
         data["measurement_self"] = torch.cat([x0bar[..., :3], x0bar[..., 3:] / x0bar[..., 3:].norm(dim=-1, keepdim=True)], dim=-1)
         self.data = data
+
+
+def window_counts(num_episodes, horizon, sequence_length, stride):
+    """(K, M): start positions per episode K = (T - S) // stride + 1 and windows M = E K of `num_episodes` episodes of `horizon`
+    timesteps cut into windows of `sequence_length` whose starts lie `stride` apart (a tail shorter than a window is not a window)"""
+    e, t, s, k = int(num_episodes), int(horizon), int(sequence_length), int(stride)
+    if k < 1:
+        raise ValueError("the window stride must be at least 1; got {!r}".format(stride))
+    if s < 1 or s > t:
+        raise ValueError("a window of {} timesteps does not fit episodes of {}".format(s, t))
+    if e < 1:
+        raise ValueError("no episodes are selected ({!r})".format(num_episodes))
+    per_episode = (t - s) // k + 1
+    return per_episode, e * per_episode
+
+
+class ResidentEpisodeDataset(RecordedEpisodeDataset):
+    """RecordedEpisodeDataset with the whole file resident in device memory: same file format, same constructor plus `device`, same
+    `refresh_data` -- the next `num_episodes` episodes in file order, wrapping, with measurement noise from the same host generator, so
+    the measurements equal the parent's for the same seed and call sequence.  The arrays are uploaded ONCE, raw; a refresh writes the
+    selected episode numbers (`sel`) and their measurements into fixed device buffers in place, so a captured step sees it.  The
+    measurement pool is laid out like the others, (E_file, T, 7): one (episode, timestep) index addresses every array.
+    `chunk(t0, S)` is the lockstep batch the parent would have staged, gathered on the device (rpe_gather_rows), which train() and
+    evaluate_episodes prefer; `sampler(...)` draws shuffled minibatches of any size (WindowSampler).  `__getitem__` returns device
+    tensors."""
+
+    def __init__(self, path, use_depth=False, obj_name=None, seed=1234, device="cuda"):
+        super().__init__(path, use_depth=use_depth, obj_name=obj_name, seed=seed)
+        self.device = torch.device(device)
+        self._true_self_host = self.episodes["true_self"]     # the noise is drawn on the host, as the parent draws it
+        self.pool = {k: v.to(self.device).contiguous() for k, v in self.episodes.items()}
+        self.pool["measurement_self"] = self.pool["true_self"].clone()   # only the selected episodes' rows are ever read
+        self.episodes = None                                  # (the host copy of the pixels is not kept)
+        self.sel = torch.zeros(self.num_recorded, dtype=torch.int32, device=self.device)   # the first num_selected entries count
+        self.num_selected = 0
+        self.selected = []
+
+    def __len__(self):
+        return self.env.horizon
+
+    def refresh_data(self, num_episodes, camera_name=None, noise_scale=0.001):
+        if num_episodes > self.num_recorded:
+            raise ValueError("{} holds {} episodes; {} were asked for".format(self.path, self.num_recorded, num_episodes))
+        sel = (torch.arange(num_episodes) + self._next) % self.num_recorded
+        self._next = int(self._next + num_episodes) % self.num_recorded
+        self.selected = sel.tolist()
+        x0 = self._true_self_host[sel]
+        x0bar = x0 + (noise_scale ** 0.5) * torch.randn(x0.shape, generator=self._gen)
+        meas = torch.cat([x0bar[..., :3], x0bar[..., 3:] / x0bar[..., 3:].norm(dim=-1, keepdim=True)], dim=-1)
+        sel_dev = sel.to(self.device)
+        self.sel[:num_episodes].copy_(sel_dev.to(torch.int32))                      # in place: captured launches read these buffers
+        self.pool["measurement_self"].index_copy_(0, sel_dev, meas.to(self.device))
+        self.num_selected = int(num_episodes)
+
+    def _need_refresh(self):
+        if self.num_selected < 1:
+            raise ValueError("{}: refresh_data has not selected any episodes yet".format(type(self).__name__))
+
+    def _batch(self, index, length, out=None):
+        """the six-tuple (img, depth, x0bar, x0, x1, obj), time-major (length, N, ...), of the windows `index` names; fields the
+        file or the model does not have are None"""
+        from .. import ops
+        t = self.env.horizon
+        keys = ("imgs", "depths" if self.use_depth else None, "measurement_self", "true_self", "true_other" if self.is_two_arm else None,
+                "true_obj" if self.obj_name is not None else None)
+        return tuple(None if k is None else ops.gather_rows(self.pool[k], index, length, t, out=None if out is None else out[i])
+                     for i, k in enumerate(keys))
+
+    def chunk(self, t0, length):
+        """Time-major chunk (S, N, ...) of timesteps [t0, t0 + length) of the selected episodes: what RecordedEpisodeDataset hands
+        train() through _host_chunks and FramePrefetcher, gathered on the device."""
+        self._need_refresh()
+        if not (0 <= t0 and length >= 1 and t0 + length <= self.env.horizon):
+            raise ValueError("chunk [{}, {}) leaves the episodes' {} timesteps".format(t0, t0 + length, self.env.horizon))
+        e = self.num_selected
+        index = torch.empty(1 + 2 * e, dtype=torch.int32, device=self.device)
+        index[0] = 0
+        index[1::2] = self.sel[:e]
+        index[2::2] = int(t0)
+        return self._batch(index, length)
+
+    def __getitem__(self, t):
+        """the reference's 6-tuple of all selected episodes at timestep t, device tensors (absent fields: empty, as the parent's)"""
+        img, depth, x0bar, x0, x1, obj = (None if v is None else v[0] for v in self.chunk(int(t), 1))
+        return (img, depth if depth is not None else torch.empty(0, device=self.device), x0bar, x0,
+                x1 if x1 is not None else torch.empty_like(x0), obj if obj is not None else torch.empty_like(x0))
+
+    def sampler(self, batch_size, sequence_length=1, stride=None, shuffle=True, seed=0):
+        """-> WindowSampler over the episodes the last refresh_data selected"""
+        return WindowSampler(self, batch_size, sequence_length, stride, shuffle, seed)
+
+
+class WindowSampler:
+    """Shuffled minibatches of `batch_size` windows of `sequence_length` consecutive timesteps from a ResidentEpisodeDataset, drawn
+    on the device (rpe_sample_windows + rpe_gather_rows; DESIGN.md "Minibatch sampling").  stride=None: window starts
+    `sequence_length` apart -- the reference's chunk grid, in shuffled order; stride=1: every offset.  An epoch is the M = E K windows
+    of the E selected episodes, each visited once, under a keyed permutation that changes with the epoch; a batch may straddle two
+    epochs.  The order is a function of (seed, step) alone; the step counter lives in device memory and every call advances it, also
+    a call replayed from a captured graph.  A call returns the six-tuple (img, depth, x0bar, x0, x1, obj), time-major (S, N, ...),
+    in buffers the sampler owns: the next call overwrites them, and a captured consumer keeps their addresses.  refresh_data between
+    calls changes the episodes and measurements the next call reads (the same number of episodes must stay selected).
+
+        sampler = dataset.sampler(256, shuffle=True, seed=0)
+        for _ in range(sampler.steps_per_epoch):
+            img, depth, x0bar, x0, x1, obj = sampler()
+    """
+
+    def __init__(self, dataset, batch_size, sequence_length=1, stride=None, shuffle=True, seed=0):
+        dataset._need_refresh()
+        self.dataset = dataset
+        self.batch_size, self.sequence_length = int(batch_size), int(sequence_length)
+        self.stride = self.sequence_length if stride is None else int(stride)
+        self.shuffle = bool(shuffle)
+        self.seed = int(seed)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must fit 64 unsigned bits; got {!r}".format(seed))
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be at least 1; got {!r}".format(batch_size))
+        self.num_episodes = dataset.num_selected
+        self.windows_per_episode, self.num_windows = window_counts(self.num_episodes, dataset.env.horizon, self.sequence_length, self.stride)
+        if self.num_windows < self.batch_size:
+            raise ValueError("a batch of {} windows needs at least as many windows; {} episodes of {} timesteps give {} (sequence_length {}, stride {})".format(
+                self.batch_size, self.num_episodes, dataset.env.horizon, self.num_windows, self.sequence_length, self.stride))
+        self.steps_per_epoch = self.num_windows // self.batch_size
+        dev = dataset.device
+        self.index = torch.zeros(1 + 2 * self.batch_size, dtype=torch.int32, device=dev)   # [0] the step used, then (episode, t0) per window
+        self._state = torch.zeros(1, dtype=torch.int32, device=dev)                         # element 0 = the step counter
+        self._out = None
+
+    def desc_fields(self):
+        """the integers of rpe_sample_desc"""
+        return dict(seed=self.seed, E=self.num_episodes, T=self.dataset.env.horizon, S=self.sequence_length, stride=self.stride, N=self.batch_size,
+                    shuffle=int(self.shuffle))
+
+    def buffers(self):
+        """the six-tuple of buffers every call writes and returns (made on first use and kept: a captured call has their addresses)"""
+        if self._out is None:
+            ds, s, n = self.dataset, self.sequence_length, self.batch_size
+            new = lambda k: torch.empty((s, n) + tuple(ds.pool[k].shape[2:]), dtype=ds.pool[k].dtype, device=ds.device)
+            self._out = (new("imgs"), new("depths") if ds.use_depth else None, new("measurement_self"), new("true_self"),
+                         new("true_other") if ds.is_two_arm else None, new("true_obj") if ds.obj_name is not None else None)
+        return self._out
+
+    def __call__(self):
+        from .. import ops
+        ds = self.dataset
+        if ds.num_selected != self.num_episodes:
+            raise ValueError("the sampler was made for {} selected episodes; refresh_data has selected {} since".format(self.num_episodes, ds.num_selected))
+        ops.sample_windows(ops.sample_desc(**self.desc_fields()), ds.sel, self._state, out=self.index)
+        return ds._batch(self.index, self.sequence_length, out=self.buffers())
+
+    @property
+    def step(self):
+        """the step counter: the number of calls so far, replays of a captured call included (reads the device)"""
+        return int(self._state[0].item()) & 0xFFFFFFFF
+
+    def state_dict(self):
+        return {"seed": self.seed, "step": self.step}
+
+    def load_state_dict(self, sd):
+        seed, step = int(sd["seed"]), int(sd["step"])
+        if not (0 <= seed < 2 ** 64 and 0 <= step < 2 ** 32):
+            raise ValueError("WindowSampler.load_state_dict: seed / step out of range: {!r}".format(sd))
+        self.seed = seed
+        self._state.fill_(step - (1 << 32) if step >= (1 << 31) else step)   # in place: a captured call keeps reading this tensor
 
 
 NOISE_SUM_STD = 147.8005   # standard deviation of the sum of four uniform bytes: sqrt(4 (256^2 - 1) / 12)

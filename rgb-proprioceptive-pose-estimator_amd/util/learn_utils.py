@@ -66,6 +66,18 @@ def _chunks(dataset, horizon, seq, use_depth):
     yield from FramePrefetcher(_host_chunks(dataset, horizon, seq, use_depth), torch.device("cuda", torch.cuda.current_device()))
 
 
+def sampled_steps_per_epoch(num_episodes, world, horizon, sequence_length, stride, batch_size):
+    """optimizer steps of one sampled `train` phase (train(batch_size=...)): every rank draws from its own shard of the episodes
+    (dist.shard_bounds), and all take the step count of the SMALLEST shard -- its windows // batch_size -- so the collectives stay
+    matched.  A function of the arguments alone: every rank computes the same number without communication."""
+    from .data_utils import window_counts
+    steps = []
+    for r in range(int(world)):
+        lo, hi = shard_bounds(num_episodes, r, world)
+        steps.append(window_counts(hi - lo, horizon, sequence_length, stride)[1] // int(batch_size))
+    return min(steps)
+
+
 def train_step(model, batch, criterion, optimizer, train_obj_pose, phase="train", grad_sync=None):
     """One iteration of the reference's hot loop (util/learn_utils.py:152-184).  Returns device scalars
     (loss, pos_err, ori_err) -- nothing is synchronised to the host."""
@@ -112,15 +124,30 @@ class GraphedTrainStep:
 
         step = GraphedTrainStep(model, criterion, optimizer, train_obj_pose=True, example_batch=batch)
         loss, pos_err, ori_err = step(batch)          # device scalars, valid until the next call
+        step = GraphedTrainStep(model, criterion, optimizer, True, None, sampler=dataset.sampler(256))
+        loss, pos_err, ori_err = step()               # every replay draws the next shuffled batch on the device
     """
 
-    def __init__(self, model, criterion, optimizer, train_obj_pose, example_batch, warmup=3, augment=None):
+    def __init__(self, model, criterion, optimizer, train_obj_pose, example_batch, warmup=3, augment=None, sampler=None):
         if dist.is_initialized() and dist.get_world_size() > 1:
             raise RuntimeError("GraphedTrainStep is single-process; data-parallel steps run eagerly")
         if not getattr(optimizer, "capturable", False):
             raise RuntimeError("GraphedTrainStep needs FusedAdam(..., capturable=True): the step count must live on the device")
         self.model, self.criterion, self.optimizer, self.train_obj_pose = model, criterion, optimizer, train_obj_pose
-        self.static = tuple(None if t is None else t.clone() for t in example_batch)
+        # sampler (util.data_utils.WindowSampler): the captured step BEGINS with the sampler's two launches, which write the sampler's
+        # own buffers -- these are the static inputs, `example_batch` may be None and __call__ takes no batch.  The sampler's step
+        # counter lives on the device, so every replay trains on the next batch of the stream (the warm-up steps advance it too).
+        self.sampler = sampler
+        if sampler is not None:
+            want = model.sequence_length if model.requires_sequence else 1
+            if sampler.sequence_length != want:
+                raise ValueError("the model takes windows of {} timesteps; the sampler draws {}".format(want, sampler.sequence_length))
+            example_batch = sampler.buffers()   # (no launch: the counter stays; the views below keep the buffers' addresses)
+            if not model.requires_sequence:
+                example_batch = tuple(None if t is None else t[0] for t in example_batch)
+            self.static = tuple(example_batch)
+        else:
+            self.static = tuple(None if t is None else t.clone() for t in example_batch)
         # augment (util.data_utils.FrameAugment): the augmentation is part of the captured step -- it reads the static raw frames and
         # writes a buffer of its own, which is what the model is fed.  Its step counter lives on the device and the captured launch
         # advances it, so every replay draws fresh parameters (the warm-up steps below advance it as well).
@@ -131,6 +158,8 @@ class GraphedTrainStep:
             self.fed = (torch.empty_like(self.static[0]),) + self.static[1:]
 
         def step():
+            if sampler is not None:
+                sampler()
             if augment is not None:
                 augment(self.static[0], out=self.fed[0])
             return train_step(model, self.fed, criterion, optimizer, train_obj_pose, "train", None)
@@ -149,10 +178,14 @@ class GraphedTrainStep:
         self.warmup_steps = warmup   # optimizer steps taken while building (the capture itself does not execute anything)
         self._keep = _graph_keepalive(model)
 
-    def __call__(self, batch):
-        for dst, src in zip(self.static, batch):
-            if dst is not None and dst is not src:   # (fill `self.static` in place to skip the copy)
-                dst.copy_(src, non_blocking=True)
+    def __call__(self, batch=None):
+        if self.sampler is not None:
+            if batch is not None:
+                raise ValueError("a GraphedTrainStep with a sampler draws its own batches: call it without one")
+        else:
+            for dst, src in zip(self.static, batch):
+                if dst is not None and dst is not src:   # (fill `self.static` in place to skip the copy)
+                    dst.copy_(src, non_blocking=True)
         self.graph.replay()
         # The replay re-ran the captured weight-packing launch, the optimizer and the BN running-statistics updates behind the
         # host's back: every plan's cached weight copies (the BN-folded inference copies above all) are stale now, exactly as
@@ -393,7 +426,8 @@ def evaluate_episodes(model, dataset, num_episodes, params, *, max_frames=256, n
 
 
 def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_per_epoch, num_val_episodes_per_epoch, params, device,
-          save_path='default', save_model=True, logging=True, *, save_optimizer=False, augment=None):
+          save_path='default', save_model=True, logging=True, *, save_optimizer=False, augment=None, batch_size=None, window_stride=None,
+          shuffle_seed=0):
     """See the module docstring.  Returns (model with the best validation weights, best validation loss).
     save_optimizer (addition; the reference saves weights only): also write `<save_path>.optim` with the optimizer state of the
     best-validation epoch so that a run can be resumed (`optimizer.load_state_dict(torch.load(path))`).
@@ -404,7 +438,17 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
     raw run.  With a schedule (lr_schedule=...) the per-epoch train line shows the current rate of the first param group.
     augment (util.data_utils.FrameAugment): applied on the device to the raw uint8 frames of the `train` phase, between their staging
     copy and the model; the `val` phase sees the recorded pixels.  Needs a dataset of raw frames (RecordedEpisodeDataset): with
-    preprocessed float images it is a ValueError."""
+    preprocessed float images it is a ValueError.
+    batch_size (default None: the lockstep walk, one chunk of every selected episode per step): the `train` phase draws shuffled
+    minibatches of `batch_size` windows of S = model.sequence_length (or 1) timesteps from the selected episodes instead
+    (dataset.sampler: util.data_utils.ResidentEpisodeDataset / WindowSampler), window starts `window_stride` apart (default S), under
+    seed `shuffle_seed` + rank; an epoch takes sampled_steps_per_epoch(...) optimizer steps and its averages divide by
+    steps * batch_size * S frames per rank.  The `val` phase is unchanged.  A dataset without `sampler` is a ValueError."""
+    if batch_size is not None and not hasattr(dataset, "sampler"):
+        raise ValueError("train(batch_size=...) draws minibatches on the device and needs a dataset with sampler() (ResidentEpisodeDataset); "
+                         "{} has none".format(type(dataset).__name__))
+    if batch_size is None and (window_stride is not None or shuffle_seed != 0):
+        raise ValueError("train(window_stride=..., shuffle_seed=...) belong to batch_size=...; without it the episodes are walked in lockstep")
     if augment is not None and getattr(dataset, "frame_dtype", torch.uint8) != torch.uint8:
         raise ValueError("train(augment=...) needs raw uint8 frames (RecordedEpisodeDataset); {} hands out {} images".format(
             type(dataset).__name__, dataset.frame_dtype))
@@ -429,6 +473,7 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
         broadcast_parameters(model._arena.flat, list(model.buffers()))
         grad_sync = GradSync(model._arena.grad).attach(model)
     seq = model.sequence_length if model.requires_sequence else 1
+    sampler = None   # made after the first `train` refresh: it reads the number of selected episodes
     fname = "{}_{}_{}hzn_{}ep_{}.pth".format(type(model).__name__, type(dataset.env).__name__, dataset.env.horizon,
                                              num_epochs * num_train_episodes_per_epoch, dt_string)
     if save_model and rank == 0:
@@ -448,8 +493,19 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
             clip_steps = 0
             horizon = len(dataset)
             ema_sd = None
+            sampled = batch_size is not None and phase == "train"
+            if sampled:
+                if sampler is None:
+                    sampler = dataset.sampler(batch_size, sequence_length=seq, stride=window_stride, shuffle=True, seed=shuffle_seed + rank)
+                steps = sampled_steps_per_epoch(num_episodes, world, horizon, seq, sampler.stride, batch_size)
+                if steps < 1:
+                    raise ValueError("the smallest shard of {} episodes over {} ranks has fewer than batch_size = {} windows".format(num_episodes, world, batch_size))
+                model.reset_initial_state(batch_size)
+                batches = (sampler() for _ in range(steps))
+            else:
+                batches = _chunks(dataset, horizon, seq, model.use_depth if hasattr(model, "use_depth") else False)
             with optimizer.averaged_weights(model) if phase == "val" and has_ema else contextlib.nullcontext():   # validate the average
-                for img, depth, x0bar, x0, x1, obj in _chunks(dataset, horizon, seq, model.use_depth if hasattr(model, "use_depth") else False):
+                for img, depth, x0bar, x0, x1, obj in batches:
                     if not model.requires_sequence:  # the reference squeezes the leading batch-of-1 dim (learn_utils.py:141-149)
                         img, x0bar, x0 = img[0], x0bar[0], x0[0]
                         depth = None if depth is None else depth[0]
@@ -470,7 +526,7 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
                 if phase == "train" and scheduled and optimizer.lr_factor is not None:
                     stats.append(optimizer.lr_factor.double().reshape(1))
                 tot = (sums if len(stats) == 1 else torch.cat(stats)).tolist()  # the one host synchronisation of the phase
-                denom = horizon * num_episodes
+                denom = steps * batch_size * seq * world if sampled else horizon * num_episodes
                 epoch_loss, epoch_pos_err, epoch_ori_err = tot[0] / denom, tot[1] / denom, tot[2] / denom
                 if phase == "val" and has_ema and epoch_loss < best_err and save_model and rank == 0:
                     ema_sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}   # taken under the swap
