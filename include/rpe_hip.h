@@ -415,6 +415,45 @@ int rpe_feature_planes_batch(int dtype, const void* x_nhwc, int B, int H, int W,
 int rpe_feature_mosaic(const float* planes, const float* minmax, int C, int H, int W, int cols, int gutter, int flip_y, unsigned char* out_u8,
                        void* stream);
 
+/* ------------------------------------------------------------------ occlusion sensitivity */
+/* No counterpart in the reference: which pixels of a raw frame the predicted pose depends on.  One rectangle of the frame at a time is
+ * set to a fill colour, the model runs, and the distance the prediction moves is the rectangle's score; the scores are spread back
+ * over the pixels and drawn over the frame.  Everything is specified to the bit ("Occlusion sensitivity").
+ * The grid: Gy = ceil((Hs - ph) / sy) + 1 by Gx = ceil((Ws - pw) / sx) + 1 rectangles, K = Gy Gx; rectangle k = gy Gx + gx has
+ * top = min(gy sy, Hs - ph), left = min(gx sx, Ws - pw): the last row and column are clamped to the frame's edge, the origins stay
+ * distinct.  A descriptor is refused (RPE_ERR_SHAPE) unless 1 <= ph <= Hs, 1 <= pw <= Ws, 1 <= sy <= ph, 1 <= sx <= pw and
+ * Hs Ws < 2^31 / 3. */
+typedef struct {
+    int Hs, Ws;               /* frame size in pixels */
+    int ph, pw;               /* rectangle size, 1 <= ph <= Hs, 1 <= pw <= Ws */
+    int sy, sx;               /* distance of rectangle origins, 1 <= sy <= ph, 1 <= sx <= pw (every pixel is covered) */
+    unsigned char fill_rgb[3];
+} rpe_occlusion_desc;
+/* host only: -> K, with *gy = Gy and *gx = Gx (either may be null); -1 with rpe_last_error set for a refused descriptor */
+long rpe_occlusion_grid(const rpe_occlusion_desc* d, int* gy, int* gx);
+/* frame: device, [Hs][Ws][3]; out: device, [B][Hs][Ws][3], disjoint from it.  Row 0 is the frame unchanged, row r >= 1 the frame with
+ * rectangle k0 + r - 1 set to fill_rgb, a row whose rectangle number is >= K the frame unchanged (the padding of the last chunk, so
+ * that every chunk runs at one batch size).  B >= 1, k0 >= 0.  16-byte loads and stores when Hs Ws 3 and both pointers are multiples
+ * of 16, 4-byte when multiples of 4, single bytes otherwise.  One launch. */
+int rpe_occlude_grid_u8(const unsigned char* frame, unsigned char* out, int B, int k0, const rpe_occlusion_desc* d, void* stream);
+/* pred: device, [n][7] poses (x, y, z, qx, qy, qz, qw); ref: device, [7].  All arithmetic in double, the results rounded once to fp32:
+ * pos[i] = sqrt(|p_i - p_ref|^2) (no epsilon); with a = q_i / |q_i|, b = q_ref / |q_ref|, dm = |a - b|, dp = |a + b|:
+ * ori[i] = 4 atan2(min(dm, dp), max(dm, dp)), the rotation angle between the two orientations in [0, pi], blind to the sign of
+ * either quaternion.  A row equal to ref gives exactly (0, 0) -- rpe_pose_errors' 2 acos(w) gives about 7e-4 rad when fp32 w is one
+ * ulp below 1.  A zero quaternion gives NaN in ori only; no other row is touched.  One sample per thread, grid-stride, n >= 1. */
+int rpe_pose_displacement(const float* pred, const float* ref, long n, float* pos, float* ori, void* stream);
+/* scores: device, [M][K]; maps: device, [M][Hs][Ws]; minmax: device, [M][2].  Pixel (y, x) of map m is the mean of the scores of the
+ * rectangles that cover it: an fp32 sum from 0 over the covering rectangles by ascending gy, then ascending gx, one correctly rounded
+ * add each, then one correctly rounded division by their number.  A NaN score makes the pixels it covers NaN.  minmax[m] is the
+ * range of map m over its finite values ((+inf, -inf) without one; -0 == +0), as rpe_feature_planes writes it.  M >= 1. */
+int rpe_saliency_map(const float* scores, int M, const rpe_occlusion_desc* d, float* maps, float* minmax, void* stream);
+/* frame, out: device, [Hs][Ws][3]; map: device, [Hs][Ws]; minmax: device, [2] = (lo, hi); table: device, 256 x 3 bytes.  Per pixel
+ * v: t = (v - lo) / (hi - lo), k = min(255, (int)(t * 256)), every operation correctly rounded fp32 (rpe_feature_mosaic's rule;
+ * hi == lo gives k = 0); a = alpha_q8 in [0, 256], or (alpha_q8 k) >> 8 when `fade` is set; per channel
+ * out = (frame (256 - a) + table[k] a + 128) >> 8.  A non-finite v copies the frame's pixel.  Hs Ws < 2^31 / 3.  One launch. */
+int rpe_saliency_overlay_u8(const unsigned char* frame, const float* map, const float* minmax, const unsigned char* table, int Hs, int Ws,
+                            int alpha_q8, int fade, unsigned char* out, void* stream);
+
 /* replaces: nn.Linear (+ F.relu) of the proprio-fusion MLP (models/naive.py:343-345), the
  * ResNet fc (util/model_utils.py:141), the LSTM input/recurrent GEMMs and the fc heads
  * (models/time_sensitive.py:420-423,510).  y[M][N] = x[M][K] w[N][K]^T (+bias) (+addend) (relu).

@@ -48,6 +48,11 @@ class SampleDesc(Structure):
     _fields_ = [("seed", ctypes.c_ulonglong)] + [(n, c_int) for n in ("E", "T", "S", "stride", "N", "shuffle")]
 
 
+class OcclusionDesc(Structure):
+    """rpe_occlusion_desc"""
+    _fields_ = [(n, c_int) for n in ("Hs", "Ws", "ph", "pw", "sy", "sx")] + [("fill_rgb", ctypes.c_ubyte * 3)]
+
+
 P, I, L, F, D = c_void_p, c_int, c_long, c_float, c_double
 PD = POINTER(ConvDesc)
 
@@ -195,6 +200,11 @@ _SPEC = {
     "rpe_feature_planes": (I, [I, P, I, I, I, I, P, P, P]),
     "rpe_feature_planes_batch": (I, [I, P, I, I, I, I, P, P, P]),
     "rpe_feature_mosaic": (I, [P, P, I, I, I, I, I, I, P, P]),
+    "rpe_occlusion_grid": (L, [POINTER(OcclusionDesc), POINTER(c_int), POINTER(c_int)]),
+    "rpe_occlude_grid_u8": (I, [P, P, I, I, POINTER(OcclusionDesc), P]),
+    "rpe_pose_displacement": (I, [P, P, L, P, P, P]),
+    "rpe_saliency_map": (I, [P, I, POINTER(OcclusionDesc), P, P, P]),
+    "rpe_saliency_overlay_u8": (I, [P, P, P, P, I, I, I, I, P, P]),
 }
 # entry points whose int return value is data, not a status
 _NOT_STATUS = {"rpe_abi_version", "rpe_conv2d_wgrad_halo_min_width", "rpe_grad_sumsq_rows"}

@@ -3,6 +3,7 @@
 //   feature_mosaic_kernel : planes + ranges -> one uint8 colour-INDEX image, a grid of per-channel autoscaled tiles
 // Both are exact: the widening has no rounding, and the mosaic is one correctly rounded fp32 operation per step.
 #include "common.h"
+#include "minmax.h"
 
 namespace rpe {
 
@@ -10,19 +11,7 @@ constexpr int kPlaneTP = 64;             // pixels per tile: one wave writes one
 constexpr int kPlaneTC = 32;             // channels per tile
 constexpr int kPlanePitch = kPlaneTP + 1;   // LDS row pitch in dwords: the transposing writes of a 32-lane half land on 32 different banks
 
-__device__ inline bool finite_f(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
-// Order-independent float min / max through integer atomics on the value's bits: non-negative floats order like signed ints, negative
-// ones like unsigned ints reversed.  The SIGN BIT picks the form (not v >= 0): -0 then orders below +0, so the result does not depend
-// on the order blocks arrive in (min ends at -0, max at +0 when both occur).  *p starts at +inf (min) / -inf (max).
-__device__ inline void atomic_min_f(float* p, float v) {
-    if (__float_as_uint(v) >> 31) atomicMax((unsigned*)p, __float_as_uint(v));
-    else atomicMin((int*)p, __float_as_int(v));
-}
-__device__ inline void atomic_max_f(float* p, float v) {
-    if (__float_as_uint(v) >> 31) atomicMin((unsigned*)p, __float_as_uint(v));
-    else atomicMax((int*)p, __float_as_int(v));
-}
+// (finite_f, atomic_min_f, atomic_max_f: minmax.h)
 
 __global__ void __launch_bounds__(256) minmax_init_kernel(float* minmax, long n_channels) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;

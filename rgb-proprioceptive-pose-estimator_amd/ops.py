@@ -812,3 +812,97 @@ def gather_rows(pool, index, S, T, out=None):
     row_bytes = pool[0, 0].numel() * pool.element_size()
     lib.rpe_gather_rows(_p(pool), _p(_chk(out, "out")), row_bytes, int(T), _p(_chk(index, "index")), int(S), n, _stream())
     return out
+
+
+OCCLUSION_DESC_FIELDS = ("Hs", "Ws", "ph", "pw", "sy", "sx", "fill_r", "fill_g", "fill_b")
+
+
+def occlusion_desc(Hs=1, Ws=1, ph=1, pw=1, sy=1, sx=1, fill_r=124, fill_g=116, fill_b=104):
+    """rpe_occlusion_desc from plain integers; OCCLUSION_DESC_FIELDS is the order of the flat list form the `torch.ops.rpe` saliency
+    operators take"""
+    from ._lib import OcclusionDesc
+    d = OcclusionDesc()
+    for k, v in (("Hs", Hs), ("Ws", Ws), ("ph", ph), ("pw", pw), ("sy", sy), ("sx", sx)):
+        setattr(d, k, int(v))
+    for i, v in enumerate((fill_r, fill_g, fill_b)):
+        if not 0 <= int(v) <= 255:
+            raise ValueError("occlusion_desc: the fill colour is three bytes; got %r" % ((fill_r, fill_g, fill_b),))
+        d.fill_rgb[i] = int(v)
+    return d
+
+
+def occlusion_grid(desc):
+    """-> (Gy, Gx) of the descriptor's grid of rectangles (rpe_occlusion_grid, host only); ValueError for a refused descriptor"""
+    from ._lib import raw
+    gy, gx = ctypes.c_int(0), ctypes.c_int(0)
+    if raw.rpe_occlusion_grid(ctypes.byref(desc), ctypes.byref(gy), ctypes.byref(gx)) < 0:
+        raise ValueError(raw.rpe_last_error().decode())
+    return gy.value, gx.value
+
+
+def occlude_grid_u8(frame, desc, b, k0, out=None):
+    """frame uint8 (Hs, Ws, 3) contiguous -> uint8 (b, Hs, Ws, 3): row 0 the frame, row r >= 1 the frame with rectangle k0 + r - 1 of
+    the descriptor's grid set to its fill colour, rows past the last rectangle the frame again (rpe_occlude_grid_u8).  out: destination,
+    contiguous, not overlapping the frame."""
+    if frame.dtype != torch.uint8 or tuple(frame.shape) != (desc.Hs, desc.Ws, 3):
+        raise ValueError("occlude_grid_u8: frame must be uint8 (%d, %d, 3); got %s %r" % (desc.Hs, desc.Ws, frame.dtype, tuple(frame.shape)))
+    shape = (int(b), desc.Hs, desc.Ws, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=frame.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != frame.device:
+        raise ValueError("occlude_grid_u8: out must be uint8 %r on the frame's device" % (shape,))
+    lib.rpe_occlude_grid_u8(_p(_chk(frame, "frame")), _p(_chk(out, "out")), int(b), int(k0), ctypes.byref(desc), _stream())
+    return out
+
+
+def pose_displacement(pred, ref, pos=None, ori=None):
+    """pred (..., 7) fp32 contiguous, ref (7,) fp32 on the same device -> (pos (...), ori (...)): the distance and the rotation angle
+    between each pose and `ref`, computed in double and rounded once (rpe_pose_displacement); exactly (0, 0) for a row equal to ref.
+    pos / ori: contiguous fp32 destinations of pred's leading shape.  Enqueued on the current stream; nothing is read back."""
+    if pred.dim() < 1 or pred.shape[-1] != 7 or pred.numel() == 0 or ref.numel() != 7:
+        raise ValueError("pose_displacement: pred must be (..., 7) and ref (7,); got %r and %r" % (tuple(pred.shape), tuple(ref.shape)))
+    if pred.dtype != torch.float32 or ref.dtype != torch.float32 or ref.device != pred.device:
+        raise TypeError("pose_displacement: pred and ref must be fp32 on one device")
+    lead = tuple(pred.shape[:-1])
+    outs = []
+    for t, name in ((pos, "pos"), (ori, "ori")):
+        if t is None:
+            t = torch.empty(lead, dtype=torch.float32, device=pred.device)
+        elif t.dtype != torch.float32 or tuple(t.shape) != lead or t.device != pred.device:
+            raise ValueError("pose_displacement: %s must be fp32 %r on pred's device" % (name, lead))
+        outs.append(_chk(t, name))
+    lib.rpe_pose_displacement(_p(_chk(pred, "pred")), _p(_chk(ref, "ref")), pred.numel() // 7, _p(outs[0]), _p(outs[1]), _stream())
+    return outs[0], outs[1]
+
+
+def saliency_map(scores, desc):
+    """scores (M, K) or (M, Gy, Gx) fp32 contiguous -> (maps (M, Hs, Ws) fp32, minmax (M, 2) fp32): every pixel the mean of the scores of
+    the rectangles covering it, and each map's range over its finite values (rpe_saliency_map)."""
+    gy, gx = occlusion_grid(desc)
+    if scores.dtype != torch.float32 or scores.dim() not in (2, 3) or scores.numel() != scores.shape[0] * gy * gx or scores.numel() == 0:
+        raise ValueError("saliency_map: scores must be fp32 (M, %d) or (M, %d, %d); got %s %r" % (gy * gx, gy, gx, scores.dtype, tuple(scores.shape)))
+    m = scores.shape[0]
+    maps = torch.empty((m, desc.Hs, desc.Ws), dtype=torch.float32, device=scores.device)
+    minmax = torch.empty((m, 2), dtype=torch.float32, device=scores.device)
+    lib.rpe_saliency_map(_p(_chk(scores, "scores")), m, ctypes.byref(desc), _p(maps), _p(minmax), _stream())
+    return maps, minmax
+
+
+def saliency_overlay_u8(frame, smap, minmax, table, alpha_q8, fade=False):
+    """frame uint8 (Hs, Ws, 3), smap fp32 (Hs, Ws), minmax fp32 (2,), table uint8 (256, 3), all contiguous on one device -> uint8
+    (Hs, Ws, 3): the map drawn over the frame through the colour table with weight alpha_q8 / 256, or, with `fade`, a weight that
+    grows with the value (rpe_saliency_overlay_u8)."""
+    if frame.dtype != torch.uint8 or frame.dim() != 3 or frame.shape[-1] != 3 or frame.numel() == 0:
+        raise ValueError("saliency_overlay_u8: frame must be uint8 (Hs, Ws, 3); got %s %r" % (frame.dtype, tuple(frame.shape)))
+    hs, ws = frame.shape[:2]
+    dev = frame.device
+    if smap.dtype != torch.float32 or tuple(smap.shape) != (hs, ws) or minmax.dtype != torch.float32 or minmax.numel() != 2:
+        raise ValueError("saliency_overlay_u8: the map must be fp32 (%d, %d) and minmax fp32 (2,)" % (hs, ws))
+    if table.dtype != torch.uint8 or tuple(table.shape) != (256, 3):
+        raise ValueError("saliency_overlay_u8: the colour table is uint8 (256, 3)")
+    if smap.device != dev or minmax.device != dev or table.device != dev:
+        raise ValueError("saliency_overlay_u8: all tensors must be on the frame's device")
+    out = torch.empty_like(frame)
+    lib.rpe_saliency_overlay_u8(_p(_chk(frame, "frame")), _p(_chk(smap, "map")), _p(_chk(minmax, "minmax")), _p(_chk(table, "table")), hs, ws, int(alpha_q8),
+                                int(bool(fade)), _p(out), _stream())
+    return out

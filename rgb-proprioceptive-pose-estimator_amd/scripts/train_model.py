@@ -160,7 +160,7 @@ DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
 
 def build_model(args, compute_dtype):
     from rgb_proprioceptive_pose_estimator_amd import models as M
-    num_resnet_layers, feature_layer_nums = 50, (9,)
+    num_resnet_layers, feature_layer_nums = getattr(args, "resnet_layers", 50), (9,)   # (--resnet_layers: scripts/visualize_features.py)
     assert args.model in MODELS, "Error: Invalid model specified. Options are: {}".format(MODELS)
     if args.model == 'n':
         return M.NaiveEndEffectorStateEstimator(hidden_dims_pre_measurement=args.hidden_dim, hidden_dims_post_measurement=args.hidden_dim,

@@ -18,6 +18,8 @@ ResNet; models/losses.py:114-128 is the loss; util/learn_utils.py:152-184 the st
     rpe::adam_step                                  torch.optim.Adam's update of one flat fp32 tensor, in place
     rpe::augment_frames_u8                          (no counterpart: the reference does not augment) jitter, noise and erasing of raw uint8 frames
     rpe::sample_windows / gather_rows               DataLoader(shuffle=True) over episode windows resident in HBM: the batch's index, and its rows
+    rpe::occlude_grid_u8 / pose_displacement /      (no counterpart: occlusion sensitivity) a frame with one rectangle of a grid covered per row; how far
+    rpe::saliency_map / saliency_overlay_u8         each prediction moved; the scores spread over the pixels; the map drawn over the frame
 
 Importing this module needs torch only; the HIP library is loaded on the first call (ops.py), so the schemas can be inspected on a
 machine without a GPU (tests/test_host_cpu.py).
@@ -29,7 +31,8 @@ import torch
 __all__ = ["NAMES"]
 
 _NS = "rpe"
-NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step", "augment_frames_u8", "sample_windows", "gather_rows")
+NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step", "augment_frames_u8", "sample_windows", "gather_rows",
+         "occlude_grid_u8", "pose_displacement", "saliency_map", "saliency_overlay_u8")
 
 
 def _ops():
@@ -225,3 +228,58 @@ def gather_rows(pool: torch.Tensor, index: torch.Tensor, S: int, T: int) -> torc
 @gather_rows.register_fake
 def _(pool, index, S, T):
     return pool.new_empty((S, (index.shape[0] - 1) // 2) + tuple(pool.shape[2:]))
+
+
+# ---- occlusion sensitivity -----------------------------------------------------------------------------------------------------
+def _occlusion_desc(name, desc):
+    ops = _ops()
+    if len(desc) != len(ops.OCCLUSION_DESC_FIELDS):
+        raise ValueError("%s: desc has %d integers (%s)" % (name, len(ops.OCCLUSION_DESC_FIELDS), ", ".join(ops.OCCLUSION_DESC_FIELDS)))
+    return ops.occlusion_desc(**dict(zip(ops.OCCLUSION_DESC_FIELDS, desc)))
+
+
+@torch.library.custom_op(_NS + "::occlude_grid_u8", mutates_args=(), device_types="cuda")
+def occlude_grid_u8(frame: torch.Tensor, desc: List[int], B: int, k0: int) -> torch.Tensor:
+    """frame uint8 (Hs, Ws, 3) -> (B, Hs, Ws, 3): row 0 the frame, row r >= 1 the frame with rectangle k0 + r - 1 covered; desc: the
+    integers of rpe_occlusion_desc in the order of ops.OCCLUSION_DESC_FIELDS"""
+    return _ops().occlude_grid_u8(frame, _occlusion_desc("occlude_grid_u8", desc), B, k0)
+
+
+@occlude_grid_u8.register_fake
+def _(frame, desc, B, k0):
+    return frame.new_empty((B,) + tuple(frame.shape))
+
+
+@torch.library.custom_op(_NS + "::pose_displacement", mutates_args=(), device_types="cuda")
+def pose_displacement(pred: torch.Tensor, ref: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """pred (..., 7), ref (7,) fp32 -> (distance (...), rotation angle in radians (...)) of every pose from ref; exactly 0 for an equal row"""
+    pos, ori = _ops().pose_displacement(pred, ref)
+    return pos, ori
+
+
+@pose_displacement.register_fake
+def _(pred, ref):
+    return pred.new_empty(pred.shape[:-1]), pred.new_empty(pred.shape[:-1])
+
+
+@torch.library.custom_op(_NS + "::saliency_map", mutates_args=(), device_types="cuda")
+def saliency_map(scores: torch.Tensor, desc: List[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """scores (M, K) or (M, Gy, Gx) fp32 -> (maps (M, Hs, Ws), minmax (M, 2)): per pixel the mean score of the covering rectangles"""
+    maps, minmax = _ops().saliency_map(scores, _occlusion_desc("saliency_map", desc))
+    return maps, minmax
+
+
+@saliency_map.register_fake
+def _(scores, desc):
+    return scores.new_empty((scores.shape[0], desc[0], desc[1])), scores.new_empty((scores.shape[0], 2))
+
+
+@torch.library.custom_op(_NS + "::saliency_overlay_u8", mutates_args=(), device_types="cuda")
+def saliency_overlay_u8(frame: torch.Tensor, smap: torch.Tensor, minmax: torch.Tensor, table: torch.Tensor, alpha_q8: int, fade: bool) -> torch.Tensor:
+    """frame uint8 (Hs, Ws, 3), smap fp32 (Hs, Ws), minmax fp32 (2,), table uint8 (256, 3) -> the map drawn over the frame, uint8 (Hs, Ws, 3)"""
+    return _ops().saliency_overlay_u8(frame, smap, minmax, table, alpha_q8, fade)
+
+
+@saliency_overlay_u8.register_fake
+def _(frame, smap, minmax, table, alpha_q8, fade):
+    return torch.empty_like(frame)

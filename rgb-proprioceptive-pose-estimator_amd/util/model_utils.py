@@ -25,6 +25,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..engine import ResNet50Trunk
+from .data_utils import ERASE_FILL_MEAN
 
 # An ImageNet checkpoint in torchvision's resnet50 state_dict format, if one is available locally.
 # The reference fetches it over the network (torchvision pretrained=True); there is no egress here.
@@ -244,3 +245,204 @@ def visualize_layer(model, layer, img, depth=None, *, out=None):
     plt.setp(plt.gcf().get_axes(), xticks=[], yticks=[])
     plt.show()
     return None
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# occlusion sensitivity (no counterpart in the reference): which pixels of a raw frame the predicted pose depends on
+# ---------------------------------------------------------------------------------------------------------------------------------
+SALIENCY_KINDS = ("position", "orientation")
+
+
+def _yx_pair(v, name):
+    if isinstance(v, (tuple, list)):
+        if len(v) != 2:
+            raise ValueError("{} is an int or a (y, x) pair; got {!r}".format(name, v))
+        y, x = v
+    else:
+        y = x = v
+    if int(y) != y or int(x) != x:
+        raise ValueError("{} must be whole numbers of pixels; got {!r}".format(name, v))
+    return int(y), int(x)
+
+
+def occlusion_grid(hs, ws, patch, stride):
+    """The grid of rectangles of an occlusion-sensitivity map of an hs x ws frame -> (Gy, Gx, tops, lefts).  `patch` and `stride` are
+    an int or a (y, x) pair.  Gy = ceil((hs - ph) / sy) + 1 rows of rectangles, row gy at tops[gy] = min(gy * sy, hs - ph): the last
+    row is clamped to the frame's edge; columns alike.  Rectangle k = gy * Gx + gx.  Pure host code (csrc/saliency.hip and
+    rpe_occlusion_grid apply the same rule).  ValueError unless 1 <= patch <= frame and 1 <= stride <= patch on both axes (a stride
+    beyond the rectangle would leave pixels that no rectangle covers)."""
+    (ph, pw), (sy, sx) = _yx_pair(patch, "patch"), _yx_pair(stride, "stride")
+    hs, ws = int(hs), int(ws)
+    if hs < 1 or ws < 1:
+        raise ValueError("the frame size must be positive; got {}x{}".format(hs, ws))
+    if not (1 <= ph <= hs and 1 <= pw <= ws):
+        raise ValueError("the rectangle must be at least 1x1 and no larger than the {}x{} frame; got patch {}x{}".format(hs, ws, ph, pw))
+    if not (1 <= sy <= ph and 1 <= sx <= pw):
+        raise ValueError("the stride must be at least 1 and no larger than the rectangle ({}x{}), so that every pixel is covered; got stride "
+                         "{}x{}".format(ph, pw, sy, sx))
+    if hs * ws * 3 >= 2 ** 31:
+        raise ValueError("frames of {}x{} pixels are too large (hs * ws must stay below 2^31 / 3)".format(hs, ws))
+    gy, gx = -(-(hs - ph) // sy) + 1, -(-(ws - pw) // sx) + 1
+    return gy, gx, [min(g * sy, hs - ph) for g in range(gy)], [min(g * sx, ws - pw) for g in range(gx)]
+
+
+class OcclusionSensitivity:
+    """What `occlusion_sensitivity` returns.  Index 0 of `scores`, `maps` and `minmax` is position (the pose's own length unit), index 1
+    orientation (radians).
+        scores   (2, Gy, Gx) fp32, device: how far the prediction moved with rectangle (gy, gx) covered (with `truth`: the change in error)
+        maps     (2, Hs, Ws) fp32, device: per pixel the mean score of the rectangles covering it
+        minmax   (2, 2) fp32, device: each map's (lowest, highest) finite value
+        baseline (7,) fp32, device: the prediction for the frame as it is
+        patch, stride (y, x) pairs; grid = (Gy, Gx); fill the three bytes the rectangles were set to"""
+
+    def __init__(self, scores, maps, minmax, baseline, patch, stride, grid, fill):
+        self.scores, self.maps, self.minmax, self.baseline = scores, maps, minmax, baseline
+        self.patch, self.stride, self.grid, self.fill = tuple(patch), tuple(stride), tuple(grid), tuple(fill)
+
+
+def _single_frame(img):
+    if not isinstance(img, torch.Tensor):
+        raise ValueError("img must be one raw uint8 frame (Hs, Ws, 3) as a tensor")
+    if img.dtype != torch.uint8:
+        raise ValueError("occlusion sensitivity works on one RAW uint8 frame (Hs, Ws, 3): the rectangles are defined on the recorded frame, in "
+                         "front of the trunk's resize / crop / normalise staging; got a {} image".format(str(img.dtype).split(".")[-1]))
+    if img.dim() < 3 or img.shape[-1] != 3 or any(n != 1 for n in img.shape[:-3]):
+        raise ValueError("img must be one frame (Hs, Ws, 3), leading dimensions of size 1 allowed; got shape {}".format(tuple(img.shape)))
+    return img.reshape(img.shape[-3:]).contiguous()
+
+
+def occlusion_sensitivity(model, img, depth=None, self_measurement=None, *, patch=32, stride=16, fill=ERASE_FILL_MEAN, truth=None, batch=64, output=-1):
+    """Occlusion sensitivity of `model`'s predicted pose for one frame -> OcclusionSensitivity.
+
+    One rectangle of the grid (`occlusion_grid`) at a time is set to the colour `fill` (default: util.data_utils.ERASE_FILL_MEAN, the
+    colour --aug_erase_prob fills with), the model predicts, and the rectangle's score is how far the prediction moved: the distance
+    in position and the rotation angle in orientation (rpe_pose_displacement; exactly 0 where the prediction did not change).  With
+    `truth` (7,) the score is the distance to `truth` minus the unoccluded prediction's distance to `truth`: the signed change in error.
+
+    img: one raw uint8 frame (Hs, Ws, 3) on the model's device; float images raise ValueError.  depth / self_measurement: the frame's
+    depth image and measured pose, repeated for every row; depth is NOT occluded (the choice util.data_utils.FrameAugment makes: its
+    erasing covers the colour frame only).  self_measurement=None stands for the identity pose (0, 0, 0, 0, 0, 0, 1).  output: which of
+    a tuple of outputs to score, -1 the last (the two-arm models' own-arm head is 0).
+
+    The K rectangles run in chunks of B = min(batch, 1 + K) rows: row 0 of EVERY chunk is the frame as it is and the last chunk is
+    padded with further copies, so that all forwards run at one batch size -- the engine picks its reduction order by the number of
+    rows, and predictions from different batch sizes are not comparable bit for bit.  The reference prediction is row 0 of the first
+    chunk.  Sequence models are called with S = 1, N = B and `rollout` off, so every row starts from the zero state and the carried
+    (h, c) are neither read nor written.  With its inputs on the device the call makes no host synchronisation; model.training, model.rollout, the carried state,
+    parameters and buffers are left as they were.  The call may create one engine plan of batch B, which under
+    ResNet50Trunk.max_plans can evict the least recently used plan."""
+    frame = _single_frame(img)
+    hs, ws = frame.shape[:2]
+    gy, gx, _, _ = occlusion_grid(hs, ws, patch, stride)
+    (ph, pw), (sy, sx) = _yx_pair(patch, "patch"), _yx_pair(stride, "stride")
+    fill = tuple(int(c) for c in fill)
+    if len(fill) != 3:
+        raise ValueError("fill is three bytes (r, g, b); got {!r}".format(fill))
+    if int(batch) < 2:
+        raise ValueError("batch must be at least 2 (the unoccluded frame and one rectangle); got {!r}".format(batch))
+    dev = frame.device
+    if truth is not None:
+        truth = torch.as_tensor(truth, dtype=torch.float32).to(dev).reshape(-1).contiguous()
+        if truth.numel() != 7:
+            raise ValueError("truth is one pose (7,); got {} values".format(truth.numel()))
+    desc = ops.occlusion_desc(hs, ws, ph, pw, sy, sx, *fill)
+    k = gy * gx
+    b = min(int(batch), 1 + k)
+    per = b - 1
+    nchunks = -(-k // per)
+    seq = bool(getattr(model, "requires_sequence", False))
+    lead = (1, b) if seq else (b,)
+
+    def rows_of(t, tail, name):   # one frame's tensor, repeated for every row of a chunk
+        t = t.to(dev)
+        if t.numel() != int(np.prod(tail)):
+            raise ValueError("{} must hold one frame's {} values; got shape {}".format(name, "x".join(map(str, tail)), tuple(t.shape)))
+        return t.reshape((1,) * len(lead) + tuple(tail)).expand(lead + tuple(tail)).contiguous()
+
+    if self_measurement is None:   # the identity pose, made on the device: no copy from the host
+        self_measurement = torch.zeros(7, dtype=torch.float32, device=dev)
+        self_measurement[6:].fill_(1.0)
+    x0bar = rows_of(torch.as_tensor(self_measurement, dtype=torch.float32), (7,), "self_measurement")
+    if depth is not None:
+        d3 = tuple(depth.shape[-3:]) if depth.dim() >= 3 else (1,) + tuple(depth.shape)
+        depth = rows_of(depth, d3, "depth")
+
+    batch_u8 = torch.empty(lead + (hs, ws, 3), dtype=torch.uint8, device=dev)
+    dist = torch.empty((2, nchunks, b), dtype=torch.float32, device=dev)
+    was_training, was_rollout = model.training, model.rollout
+    first = None
+    model.eval()
+    model.rollout = False
+    try:
+        with torch.no_grad():
+            for c in range(nchunks):
+                ops.occlude_grid_u8(frame, desc, b, c * per, out=batch_u8.view(b, hs, ws, 3))
+                out = model(batch_u8, depth, x0bar)
+                if isinstance(out, (tuple, list)):
+                    out = out[output]
+                pred = out.reshape(b, 7)
+                if pred.dtype != torch.float32 or not pred.is_contiguous():
+                    pred = pred.float().contiguous()
+                if first is None:
+                    first = pred   # (kept alive: the reference pose is read from its row 0 by every chunk)
+                ops.pose_displacement(pred, first[0] if truth is None else truth, pos=dist[0, c], ori=dist[1, c])
+    finally:
+        model.rollout = was_rollout
+        model.train(was_training)
+    if truth is not None:
+        dist = dist - dist[:, 0, 0].reshape(2, 1, 1)
+    scores = dist[:, :, 1:].reshape(2, nchunks * per)[:, :k].contiguous().view(2, gy, gx)
+    maps, minmax = ops.saliency_map(scores, desc)
+    return OcclusionSensitivity(scores, maps, minmax, first[0].clone(), (ph, pw), (sy, sx), (gy, gx), fill)
+
+
+_TABLES = {}
+
+
+def _device_colour_table(device):
+    """colour_table() on `device`, uploaded once"""
+    key = (device.type, device.index)
+    t = _TABLES.get(key)
+    if t is None:
+        t = _TABLES[key] = torch.from_numpy(np.ascontiguousarray(colour_table(), dtype=np.uint8)).to(device)
+    return t
+
+
+def _saliency_index(which):
+    if which not in SALIENCY_KINDS:
+        raise ValueError("which is one of {}; got {!r}".format(SALIENCY_KINDS, which))
+    return SALIENCY_KINDS.index(which)
+
+
+def render_saliency(result, frame, which="position", *, alpha=0.5, fade=False):
+    """The map `which` ('position' / 'orientation') of an OcclusionSensitivity drawn over its frame -> uint8 (Hs, Ws, 3) numpy array.
+    The map is autoscaled to its own range and coloured through `colour_table()`; `alpha` in [0, 1] is the weight of the colour
+    (alpha_q8 = round(alpha * 256)); with `fade` the weight grows with the value, so the cold part of the frame stays readable
+    (rpe_saliency_overlay_u8).  Pixels without a finite value show the frame."""
+    i = _saliency_index(which)
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError("alpha lies in [0, 1]; got {!r}".format(alpha))
+    frame = _single_frame(frame).to(result.maps.device)
+    if tuple(frame.shape[:2]) != tuple(result.maps.shape[1:]):
+        raise ValueError("the frame is {}x{} but the map {}x{}".format(*frame.shape[:2], *result.maps.shape[1:]))
+    out = ops.saliency_overlay_u8(frame, result.maps[i], result.minmax[i], _device_colour_table(frame.device), int(round(float(alpha) * 256)), fade)
+    return out.cpu().numpy()
+
+
+def visualize_saliency(model, img, depth=None, self_measurement=None, *, which="position", out=None, alpha=0.5, fade=False, result=None, **kwargs):
+    """Shows the occlusion-sensitivity map `which` of `model` for the frame `img` over the frame; with `out` the picture is written
+    there as a PNG and no window is opened (as `visualize_layer`).  kwargs go to `occlusion_sensitivity` (patch, stride, fill, truth,
+    batch, output); `result`: an OcclusionSensitivity of the same frame to draw instead of computing one.  Returns the result."""
+    if result is None:
+        result = occlusion_sensitivity(model, img, depth, self_measurement, **kwargs)
+    rgb = render_saliency(result, img, which, alpha=alpha, fade=fade)
+    if out is not None:
+        from PIL import Image
+        Image.fromarray(rgb).save(out, format="PNG")
+        return result
+    import matplotlib.pyplot as plt
+    plt.figure()
+    plt.imshow(rgb)
+    plt.setp(plt.gcf().get_axes(), xticks=[], yticks=[])
+    plt.show()
+    return result
