@@ -292,6 +292,25 @@ int rpe_sample_windows(const rpe_sample_desc* d, const int* sel, unsigned* state
  * are multiples of 16, 4-byte when multiples of 4, single bytes otherwise.  One launch. */
 int rpe_gather_rows(const void* pool, void* out, long row_bytes, long T, const int* index, int S, int N, void* stream);
 
+/* replaces: the measurement noise the reference draws on the host per refresh, x0bar = x0 + N(0, variance I) with the quaternion
+ * renormalised (util/data_utils.py:162-167), drawn on the device at every launch instead ("Measurement noise").  Philox4x32-10
+ * keyed by `seed`.  Lane n draws ONE scale for its whole window: index 0 when num_scales == 1, else k = (r0 num_scales) >> 32 with r0 =
+ * word 0 at counter (n, 0, step, 0x4D45414B).  Row r = s N + n, component c: words (r0, r1) at counter (r, c, step, 0x4D454153), in
+ * fp64 u1 = (r0 + 0.5) 2^-32, u2 = r1 2^-32, z = sqrt(-2 log u1) cos(2 pi u2); e[0] = z[0], e[s] = rho e[s-1] + sqrt(1 - rho^2) z[s]
+ * per lane and component (stationary, unit variance; rho = 0: e = z); v[c] = x0[r][c] + sigma[k] e[s][c]; out[r][0..2] = v[0..2],
+ * out[r][3..6] = v[3..6] / |v[3..6]|, all in fp64 and rounded to fp32 once (a zero norm gives what IEEE division gives). */
+typedef struct {
+    unsigned long long seed;   /* Philox key = (low word, high word) */
+    int S, N;                  /* rows are time-major: row s*N + n; S*N < 2^31; a flat batch is S = 1 */
+    int num_scales;            /* 1..8 */
+    double sigma[8];           /* sqrt(variance), computed on the host in double */
+    double rho;                /* 0 <= rho < 1: AR(1) coefficient along s; 0 = white */
+} rpe_measure_desc;
+/* x0, out: device, [S*N][7] fp32 (x, y, z, qx, qy, qz, qw), the same buffer or disjoint ones.  state: device, state[0] is the step
+ * counter -- the launch reads it and advances it by one (wrapping at 2^32), so a captured call draws fresh numbers at every replay.
+ * picks: device, 1 + N ints, receives [0] = the step used, [1 + n] = the scale index lane n drew.  Two launches. */
+int rpe_measurement_noise(const float* x0, float* out, const rpe_measure_desc* d, unsigned* state, int* picks, void* stream);
+
 /* ------------------------------------------------------------------ batch norm */
 /* replaces: nn.BatchNorm2d (train mode: biased batch variance, eps, momentum with
  * unbiased running variance) + the in-place nn.ReLU and `out += identity` of the

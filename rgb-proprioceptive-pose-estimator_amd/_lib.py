@@ -48,6 +48,11 @@ class SampleDesc(Structure):
     _fields_ = [("seed", ctypes.c_ulonglong)] + [(n, c_int) for n in ("E", "T", "S", "stride", "N", "shuffle")]
 
 
+class MeasureDesc(Structure):
+    """rpe_measure_desc"""
+    _fields_ = [("seed", ctypes.c_ulonglong)] + [(n, c_int) for n in ("S", "N", "num_scales")] + [("sigma", c_double * 8), ("rho", c_double)]
+
+
 class OcclusionDesc(Structure):
     """rpe_occlusion_desc"""
     _fields_ = [(n, c_int) for n in ("Hs", "Ws", "ph", "pw", "sy", "sx")] + [("fill_rgb", ctypes.c_ubyte * 3)]
@@ -104,6 +109,7 @@ _SPEC = {
     "rpe_augment_frames_u8": (I, [P, P, I, I, I, POINTER(AugmentDesc), P, P, P, P]),
     "rpe_sample_windows": (I, [POINTER(SampleDesc), P, P, P, P]),
     "rpe_gather_rows": (I, [P, P, L, L, P, I, I, P]),
+    "rpe_measurement_noise": (I, [P, P, POINTER(MeasureDesc), P, P, P]),
     "rpe_bn_finalize": (I, [P, I, I, L, P, P, P, P, P, F, F, P, P, P, P, P, P]),
     "rpe_bn_eval_affine": (I, [I, P, P, P, P, F, P, P, P]),
     "rpe_bn_apply": (I, [I, P, P, P, P, P, L, I, I, P]),

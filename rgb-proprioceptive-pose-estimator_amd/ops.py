@@ -6,6 +6,7 @@ current HIP stream to librpe_hip.so, and returns the output tensors.  Activation
 conv trunk are NHWC tensors ([B, H, W, C], contiguous) in fp32 or bf16.
 """
 import ctypes
+import math
 import os
 
 import torch
@@ -905,4 +906,70 @@ def saliency_overlay_u8(frame, smap, minmax, table, alpha_q8, fade=False):
     out = torch.empty_like(frame)
     lib.rpe_saliency_overlay_u8(_p(_chk(frame, "frame")), _p(_chk(smap, "map")), _p(_chk(minmax, "minmax")), _p(_chk(table, "table")), hs, ws, int(alpha_q8),
                                 int(bool(fade)), _p(out), _stream())
+    return out
+
+
+MEASURE_MAX_SCALES = 8
+# the flat list form `torch.ops.rpe.measurement_noise` takes: these five numbers, then the 1..8 variances (the seed travels as two
+# 32-bit words because a double does not hold 64 bits)
+MEASURE_DESC_NUMBERS = ("seed_lo", "seed_hi", "S", "N", "correlation")
+
+
+def measure_scales(scales):
+    """`scales` -- one variance or a sequence of 1..8 -- as a tuple of floats; ValueError unless each is finite and not negative"""
+    try:
+        vals = tuple(float(v) for v in scales)
+    except TypeError:
+        vals = (float(scales),)
+    if not 1 <= len(vals) <= MEASURE_MAX_SCALES:
+        raise ValueError("measurement noise takes 1..%d scales; got %d" % (MEASURE_MAX_SCALES, len(vals)))
+    for v in vals:
+        if not (v >= 0.0 and math.isfinite(v)):
+            raise ValueError("a measurement-noise scale is a variance, finite and not negative; got %r" % (v,))
+    return vals
+
+
+def measure_desc(seed=0, S=1, N=1, scales=(0.001,), correlation=0.0):
+    """rpe_measure_desc: `scales` are VARIANCES (one or a sequence of 1..8; sigma = sqrt(variance) is taken here, in double),
+    `correlation` the AR(1) coefficient along S in [0, 1).  ValueError for anything the kernel would refuse."""
+    from ._lib import MeasureDesc
+    seed, s, n, rho = int(seed), int(S), int(N), float(correlation)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("measure_desc: seed must fit 64 unsigned bits; got %r" % (seed,))
+    if s < 1 or n < 1 or s * n >= 2 ** 31:
+        raise ValueError("measure_desc: S and N must be at least 1 and S * N below 2^31; got S = %r, N = %r" % (S, N))
+    if not 0.0 <= rho < 1.0:
+        raise ValueError("measure_desc: correlation must lie in [0, 1); got %r" % (correlation,))
+    vals = measure_scales(scales)
+    d = MeasureDesc()
+    d.seed, d.S, d.N, d.num_scales, d.rho = seed, s, n, len(vals), rho
+    for k, v in enumerate(vals):
+        d.sigma[k] = math.sqrt(v)
+    return d
+
+
+def measurement_noise(x0, desc, state, picks=None, out=None):
+    """x0 fp32 (..., 7) contiguous, desc.S * desc.N rows (x, y, z, qx, qy, qz, qw), time-major -> x0 + noise with the quaternion
+    renormalised, fp32 of the same shape (rpe_measurement_noise).  desc: measure_desc(...).  state: int32 device tensor whose
+    element 0 is the step counter; the launch advances it by one.  picks: int32 (1 + N,) device tensor receiving the step used and
+    each lane's scale index (allocated when not given).  out: destination (may be `x0` itself)."""
+    if x0.dtype != torch.float32 or x0.dim() < 2 or x0.shape[-1] != 7:
+        raise ValueError("measurement_noise: x0 must be fp32 (..., 7); got %s %r" % (x0.dtype, tuple(x0.shape)))
+    _chk(x0, "x0")
+    n = int(desc.N)
+    if x0.numel() != int(desc.S) * n * 7 or x0.numel() == 0:
+        raise ValueError("measurement_noise: x0 has %d rows, the descriptor S * N = %d * %d" % (x0.numel() // 7, desc.S, desc.N))
+    dev = x0.device
+    if state.dtype != torch.int32 or state.numel() < 1 or state.device != dev:
+        raise ValueError("measurement_noise: state must be an int32 tensor on x0's device")
+    if out is None:
+        out = torch.empty_like(x0)
+    elif out.dtype != torch.float32 or out.shape != x0.shape or out.device != dev:
+        raise ValueError("measurement_noise: out must be fp32 of x0's shape on its device")
+    _chk(out, "out")
+    if picks is None:
+        picks = torch.empty(1 + n, dtype=torch.int32, device=dev)
+    elif picks.dtype != torch.int32 or picks.numel() < 1 + n or picks.device != dev:
+        raise ValueError("measurement_noise: picks must be int32 with at least %d elements on x0's device" % (1 + n))
+    lib.rpe_measurement_noise(_p(x0), _p(out), ctypes.byref(desc), _p(_chk(state, "state")), _p(_chk(picks, "picks")), _stream())
     return out

@@ -11,7 +11,8 @@ learning-rate schedule (--lr_schedule, --warmup_steps, --warmup_start_factor, --
 the on-device frame augmentation of recorded episodes (--aug_brightness, --aug_contrast, --aug_saturation, --aug_noise_std,
 --aug_erase_prob, --aug_erase_scale, --aug_erase_fill, --aug_per_frame, --aug_seed; all off by default, they need --episodes);
 --resident (the --episodes file lives in HBM) and, with it, --batch_size, --window_stride, --shuffle_seed (shuffled minibatches drawn on the
-device instead of one chunk of every episode per step).
+device instead of one chunk of every episode per step); --meas_noise_device / --meas_noise_scales, --meas_noise_correlation,
+--meas_noise_seed (the measurement noise of the `train` phase drawn on the device, fresh at every step; off by default, any dataset).
 
 Multi-GPU: launch with `python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 scripts/train_model.py ...`;
 episodes are sharded over ranks and gradients SUM-all-reduced over RCCL.
@@ -101,7 +102,39 @@ def build_parser():
                         "drawn on the device (needs --episodes --resident; default: one chunk of every episode per step, in file order)")
     p.add_argument("--window_stride", type=int, default=None, help="sampling: distance of window starts (default: the window's length; 1 = every offset)")
     p.add_argument("--shuffle_seed", type=int, default=None, help="sampling: seed of the device sampler (default 0; rank r uses seed + r)")
+    p.add_argument("--meas_noise_device", action="store_true",
+                   help="draw the measurement noise of the train phase on the device, fresh at every step (util.data_utils.MeasurementNoise), "
+                        "with the variance --noise_scale (default: the dataset's host draw, once per refresh)")
+    p.add_argument("--meas_noise_scales", type=float, nargs="+", default=None, metavar="S",
+                   help="device measurement noise with 1..8 variances instead of --noise_scale: every window draws one of them per step")
+    p.add_argument("--meas_noise_correlation", type=float, default=None, metavar="R",
+                   help="device measurement noise: AR(1) coefficient in [0, 1) along the --sequence_length steps of a window (default 0: white)")
+    p.add_argument("--meas_noise_seed", type=int, default=None, metavar="K", help="device measurement noise: seed of the device generator (default 0; rank r uses K + r)")
     return p
+
+
+def build_measurement_noise(args, rank=0):
+    """--meas_noise_device / --meas_noise_scales / --meas_noise_correlation / --meas_noise_seed -> util.data_utils.MeasurementNoise,
+    or None when none of them is given.  Any of the four turns the device draw on; the variances default to [--noise_scale].  They
+    need no other flag: the draw takes the batch's true poses, which every dataset hands out."""
+    scales, rho, seed = (getattr(args, k, None) for k in ("meas_noise_scales", "meas_noise_correlation", "meas_noise_seed"))
+    if not getattr(args, "meas_noise_device", False) and scales is None and rho is None and seed is None:
+        return None
+    from rgb_proprioceptive_pose_estimator_amd.ops import MEASURE_MAX_SCALES
+    from rgb_proprioceptive_pose_estimator_amd.util.data_utils import MeasurementNoise
+    flag = "--meas_noise_scales" if scales is not None else "--noise_scale"
+    scales = [args.noise_scale] if scales is None else list(scales)
+    if not 1 <= len(scales) <= MEASURE_MAX_SCALES:
+        raise SystemExit("%s takes 1..%d variances; got %d" % (flag, MEASURE_MAX_SCALES, len(scales)))
+    if not all(v >= 0.0 and v != float("inf") for v in scales):
+        raise SystemExit("%s: a variance is finite and not negative; got %r" % (flag, scales))
+    rho = 0.0 if rho is None else rho
+    if not 0.0 <= rho < 1.0:
+        raise SystemExit("--meas_noise_correlation must lie in [0, 1); got %r" % rho)
+    seed = (seed or 0)
+    if not (0 <= seed and seed + rank < 2 ** 64):
+        raise SystemExit("--meas_noise_seed must fit 64 unsigned bits (rank r uses K + r); got %d" % seed)
+    return MeasurementNoise(scales, correlation=rho, seed=seed + rank)
 
 
 def build_sampling(args):
@@ -237,6 +270,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     build_augment(args)   # (a flag that cannot be honoured stops the run before anything is built)
     sampling = build_sampling(args)
+    build_measurement_noise(args)
     from rgb_proprioceptive_pose_estimator_amd.dist import init_from_env
     from rgb_proprioceptive_pose_estimator_amd.models import PoseDistanceLoss
     from rgb_proprioceptive_pose_estimator_amd.util.data_utils import RecordedEpisodeDataset, ResidentEpisodeDataset, SyntheticEpisodeDataset
@@ -276,7 +310,8 @@ def main(argv=None):
         print("Training...")
     return train(model=model, dataset=dataset, criterion=criterion, optimizer=optimizer, num_epochs=args.n_epochs,
                  num_train_episodes_per_epoch=args.n_train_episodes_per_epoch, num_val_episodes_per_epoch=args.n_val_episodes_per_epoch,
-                 params=params, device=device, save_model=not args.no_save, augment=build_augment(args, rank), **sampling)
+                 params=params, device=device, save_model=not args.no_save, augment=build_augment(args, rank),
+                 measurement_noise=build_measurement_noise(args, rank), **sampling)
 
 
 if __name__ == "__main__":

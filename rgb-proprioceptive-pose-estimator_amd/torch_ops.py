@@ -18,6 +18,7 @@ ResNet; models/losses.py:114-128 is the loss; util/learn_utils.py:152-184 the st
     rpe::adam_step                                  torch.optim.Adam's update of one flat fp32 tensor, in place
     rpe::augment_frames_u8                          (no counterpart: the reference does not augment) jitter, noise and erasing of raw uint8 frames
     rpe::sample_windows / gather_rows               DataLoader(shuffle=True) over episode windows resident in HBM: the batch's index, and its rows
+    rpe::measurement_noise                          x0 + sqrt(scale) * randn_like(x0) with the quaternion renormalised (util/data_utils.py:162-167), drawn on the device
     rpe::occlude_grid_u8 / pose_displacement /      (no counterpart: occlusion sensitivity) a frame with one rectangle of a grid covered per row; how far
     rpe::saliency_map / saliency_overlay_u8         each prediction moved; the scores spread over the pixels; the map drawn over the frame
 
@@ -32,7 +33,7 @@ __all__ = ["NAMES"]
 
 _NS = "rpe"
 NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step", "augment_frames_u8", "sample_windows", "gather_rows",
-         "occlude_grid_u8", "pose_displacement", "saliency_map", "saliency_overlay_u8")
+         "measurement_noise", "occlude_grid_u8", "pose_displacement", "saliency_map", "saliency_overlay_u8")
 
 
 def _ops():
@@ -228,6 +229,27 @@ def gather_rows(pool: torch.Tensor, index: torch.Tensor, S: int, T: int) -> torc
 @gather_rows.register_fake
 def _(pool, index, S, T):
     return pool.new_empty((S, (index.shape[0] - 1) // 2) + tuple(pool.shape[2:]))
+
+
+# ---- measurement noise ---------------------------------------------------------------------------------------------------------
+@torch.library.custom_op(_NS + "::measurement_noise", mutates_args=("state",), device_types="cuda")
+def measurement_noise(x0: torch.Tensor, desc: List[float], state: torch.Tensor) -> torch.Tensor:
+    """x0 fp32 (S, N, 7) or (B, 7) -> x0 + noise with the quaternion renormalised; desc: the numbers of ops.MEASURE_DESC_NUMBERS
+    (seed low word, seed high word, S, N, correlation), then the 1..8 variances; state: int32, element 0 is the step counter,
+    advanced by one"""
+    ops = _ops()
+    k = len(ops.MEASURE_DESC_NUMBERS)
+    if not k + 1 <= len(desc) <= k + ops.MEASURE_MAX_SCALES:
+        raise ValueError("measurement_noise: desc is %s and then 1..%d variances" % (", ".join(ops.MEASURE_DESC_NUMBERS), ops.MEASURE_MAX_SCALES))
+    lo, hi, s, n = (int(v) for v in desc[:4])
+    if not (0 <= lo < 2 ** 32 and 0 <= hi < 2 ** 32):
+        raise ValueError("measurement_noise: the seed travels as two 32-bit words; got %r, %r" % (desc[0], desc[1]))
+    return ops.measurement_noise(x0, ops.measure_desc(seed=lo | (hi << 32), S=s, N=n, scales=list(desc[k:]), correlation=desc[4]), state)
+
+
+@measurement_noise.register_fake
+def _(x0, desc, state):
+    return torch.empty_like(x0)
 
 
 # ---- occlusion sensitivity -----------------------------------------------------------------------------------------------------

@@ -9,7 +9,8 @@ episodes at timestep t, util/data_utils.py:62-73), the 6-tuple, `refresh_data`, 
 proprioception = truth + N(0, noise_scale I) with the quaternion renormalised, util/data_utils.py:162-176),
 generated directly in HBM.  RecordedEpisodeDataset reads episodes recorded from the simulator elsewhere back from a file, raw, and
 leaves every image transform to the device; ResidentEpisodeDataset keeps that file in HBM and WindowSampler draws shuffled minibatches
-from it on the device.
+from it on the device.  FrameAugment and MeasurementNoise draw what varies between train steps -- the frame augmentation and the
+measurement noise -- on the device as well, keyed by (seed, step).
 """
 import types
 
@@ -566,6 +567,86 @@ class FrameAugment:
         seed, step = int(sd["seed"]), int(sd["step"])
         if not (0 <= seed < 2 ** 64 and 0 <= step < 2 ** 32):
             raise ValueError("FrameAugment.load_state_dict: seed / step out of range: {!r}".format(sd))
+        self.seed = seed
+        self._step0 = step
+        if self._state is not None:   # in place: a captured call keeps reading this tensor
+            self._state.fill_(step - (1 << 32) if step >= (1 << 31) else step)
+
+
+class MeasurementNoise:
+    """The measurement of the robot's own pose, x0bar = x0 + N(0, scale I) with the quaternion renormalised (what `refresh_data`
+    draws on the host once per refresh, util/data_utils.py:162-167 of the reference), drawn on the device at EVERY call
+    (rpe_measurement_noise; DESIGN.md "Measurement noise").  `scale` is a variance, as `noise_scale` is, or a sequence of 1..8
+    variances: every lane then draws one of them per call, for its whole window.  `correlation` in [0, 1) is the AR(1) coefficient of
+    the noise along the S timesteps of a window (0: white); it restarts with every window, stationary with unit variance.  The random
+    numbers are a function of (seed, step); the step counter lives in device memory and every call advances it, also a call replayed
+    from a captured graph.  Takes a contiguous fp32 device tensor (B, 7) -- lanes = rows -- or (S, N, 7), time-major.
+
+        noise = MeasurementNoise([0.001, 0.01], correlation=0.5, seed=0)
+        x0bar = noise(x0)                   # a new tensor; noise(x0, out=buf) writes buf (buf may be x0)
+    """
+
+    def __init__(self, scale=0.001, correlation=0.0, seed=0):
+        from ..ops import measure_scales
+        self.scales = measure_scales(scale)
+        self.correlation = float(correlation)
+        if not 0.0 <= self.correlation < 1.0:
+            raise ValueError("correlation must lie in [0, 1); got {!r}".format(correlation))
+        self.seed = int(seed)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must fit 64 unsigned bits; got {!r}".format(seed))
+        self.last_picks = None      # device table of the last call: [0] the step used, then each lane's scale index
+        self._state = None          # int32 device tensor, element 0 = the step counter
+        self._step0 = 0             # the counter while there is no device tensor yet
+        self._picks = None
+
+    @staticmethod
+    def check_poses(x0):
+        """ValueError unless `x0` is a contiguous fp32 device tensor (B, 7) or (S, N, 7); -> (S, N)"""
+        if not isinstance(x0, torch.Tensor) or x0.dtype != torch.float32:
+            raise ValueError("MeasurementNoise takes fp32 poses; got {}".format(getattr(x0, "dtype", type(x0))))
+        if x0.dim() not in (2, 3) or x0.shape[-1] != 7 or not x0.is_contiguous() or x0.numel() == 0:
+            raise ValueError("MeasurementNoise takes poses (B, 7) or (S, N, 7), contiguous; got {}".format(tuple(x0.shape)))
+        if not x0.is_cuda:
+            raise ValueError("MeasurementNoise runs on the device only (there is no CPU path); got a {} tensor".format(x0.device))
+        return (1, x0.shape[0]) if x0.dim() == 2 else (x0.shape[0], x0.shape[1])
+
+    def desc_fields(self, s, n):
+        """the arguments of ops.measure_desc for S = s timesteps of N = n lanes"""
+        return dict(seed=self.seed, S=int(s), N=int(n), scales=self.scales, correlation=self.correlation)
+
+    def _device_state(self, device):
+        if self._state is None or self._state.device != device:
+            step = self.step
+            self._state = torch.tensor([step - (1 << 32) if step >= (1 << 31) else step], dtype=torch.int32, device=device)
+        return self._state
+
+    def __call__(self, x0, out=None):
+        from .. import ops
+        s, n = self.check_poses(x0)
+        if out is not None and (not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or out.shape != x0.shape or out.device != x0.device
+                                or not out.is_contiguous()):
+            raise ValueError("MeasurementNoise: out must be a contiguous fp32 tensor of x0's shape on its device")
+        desc = ops.measure_desc(**self.desc_fields(s, n))
+        state = self._device_state(x0.device)
+        if self._picks is None or self._picks.numel() != 1 + n or self._picks.device != x0.device:   # kept: a captured call has its address
+            self._picks = torch.zeros(1 + n, dtype=torch.int32, device=x0.device)
+        out = ops.measurement_noise(x0, desc, state, picks=self._picks, out=out)
+        self.last_picks = self._picks
+        return out
+
+    @property
+    def step(self):
+        """the step counter: the number of calls so far, replays of a captured call included (reads the device)"""
+        return self._step0 if self._state is None else int(self._state[0].item()) & 0xFFFFFFFF
+
+    def state_dict(self):
+        return {"seed": self.seed, "step": self.step}
+
+    def load_state_dict(self, sd):
+        seed, step = int(sd["seed"]), int(sd["step"])
+        if not (0 <= seed < 2 ** 64 and 0 <= step < 2 ** 32):
+            raise ValueError("MeasurementNoise.load_state_dict: seed / step out of range: {!r}".format(sd))
         self.seed = seed
         self._step0 = step
         if self._state is not None:   # in place: a captured call keeps reading this tensor

@@ -126,9 +126,11 @@ class GraphedTrainStep:
         loss, pos_err, ori_err = step(batch)          # device scalars, valid until the next call
         step = GraphedTrainStep(model, criterion, optimizer, True, None, sampler=dataset.sampler(256))
         loss, pos_err, ori_err = step()               # every replay draws the next shuffled batch on the device
+        step = GraphedTrainStep(..., sampler=dataset.sampler(256), measurement_noise=MeasurementNoise([0.001, 0.01]))
+        loss, pos_err, ori_err = step()               # ... and fresh measurement noise on its true poses
     """
 
-    def __init__(self, model, criterion, optimizer, train_obj_pose, example_batch, warmup=3, augment=None, sampler=None):
+    def __init__(self, model, criterion, optimizer, train_obj_pose, example_batch, warmup=3, augment=None, sampler=None, measurement_noise=None):
         if dist.is_initialized() and dist.get_world_size() > 1:
             raise RuntimeError("GraphedTrainStep is single-process; data-parallel steps run eagerly")
         if not getattr(optimizer, "capturable", False):
@@ -156,10 +158,19 @@ class GraphedTrainStep:
         if augment is not None:
             augment.check_frames(self.static[0])
             self.fed = (torch.empty_like(self.static[0]),) + self.static[1:]
+        # measurement_noise (util.data_utils.MeasurementNoise): the draw is part of the captured step, after the sampler's launches -- it
+        # reads the static true poses x0 and writes a buffer of its own, which takes the place of x0bar in what the model is fed.  Its
+        # step counter lives on the device: every replay draws fresh noise (the warm-up steps advance it, the capture does not).
+        self.measurement_noise = measurement_noise
+        if measurement_noise is not None:
+            measurement_noise.check_poses(self.static[3])
+            self.fed = self.fed[:2] + (torch.empty_like(self.static[3]),) + self.fed[3:]
 
         def step():
             if sampler is not None:
                 sampler()
+            if measurement_noise is not None:
+                measurement_noise(self.static[3], out=self.fed[2])
             if augment is not None:
                 augment(self.static[0], out=self.fed[0])
             return train_step(model, self.fed, criterion, optimizer, train_obj_pose, "train", None)
@@ -427,7 +438,7 @@ def evaluate_episodes(model, dataset, num_episodes, params, *, max_frames=256, n
 
 def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_per_epoch, num_val_episodes_per_epoch, params, device,
           save_path='default', save_model=True, logging=True, *, save_optimizer=False, augment=None, batch_size=None, window_stride=None,
-          shuffle_seed=0):
+          shuffle_seed=0, measurement_noise=None):
     """See the module docstring.  Returns (model with the best validation weights, best validation loss).
     save_optimizer (addition; the reference saves weights only): also write `<save_path>.optim` with the optimizer state of the
     best-validation epoch so that a run can be resumed (`optimizer.load_state_dict(torch.load(path))`).
@@ -443,7 +454,14 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
     minibatches of `batch_size` windows of S = model.sequence_length (or 1) timesteps from the selected episodes instead
     (dataset.sampler: util.data_utils.ResidentEpisodeDataset / WindowSampler), window starts `window_stride` apart (default S), under
     seed `shuffle_seed` + rank; an epoch takes sampled_steps_per_epoch(...) optimizer steps and its averages divide by
-    steps * batch_size * S frames per rank.  The `val` phase is unchanged.  A dataset without `sampler` is a ValueError."""
+    steps * batch_size * S frames per rank.  The `val` phase is unchanged.  A dataset without `sampler` is a ValueError.
+    measurement_noise (util.data_utils.MeasurementNoise): in the `train` phase the model is fed measurement_noise(x0), drawn on the
+    device afresh at every step, in place of the dataset's x0bar (drawn on the host once per refresh); it needs the batch's x0 rows
+    only, so every dataset takes it.  The `val` phase keeps the dataset's measurements, and the dataset's own pool is not written."""
+    if measurement_noise is not None:
+        from .data_utils import MeasurementNoise
+        if not isinstance(measurement_noise, MeasurementNoise):
+            raise ValueError("train(measurement_noise=...) takes a util.data_utils.MeasurementNoise; got {!r}".format(type(measurement_noise).__name__))
     if batch_size is not None and not hasattr(dataset, "sampler"):
         raise ValueError("train(batch_size=...) draws minibatches on the device and needs a dataset with sampler() (ResidentEpisodeDataset); "
                          "{} has none".format(type(dataset).__name__))
@@ -515,6 +533,8 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
                         if img.dtype != torch.uint8:
                             raise ValueError("train(augment=...) needs raw uint8 frames; the dataset hands out {} images".format(img.dtype))
                         img = augment(img)
+                    if measurement_noise is not None and phase == "train":
+                        x0bar = measurement_noise(x0.contiguous())
                     loss, pe, oe = train_step(model, (img, depth, x0bar, x0, x1, obj), criterion, optimizer, train_obj_pose, phase, grad_sync)
                     sums += torch.stack([loss.double(), pe.double(), oe.double()])
                     if clip_sums is not None:
