@@ -10,6 +10,19 @@ namespace rpe {
 // reference: models/naive.py:223-231,318-330.  a1 = relu(bn1(conv1 x)) is [B][H][W][64] (T).
 // A group of LPP = 64/CE lanes owns one output pixel (2x2 input window).
 // ---------------------------------------------------------------------------------------------
+// A lane's share of the 1x1 conv: products and sums rounded separately, in channel order.  Left to the compiler, two taps of a window
+// were contracted to fused multiply-adds and two were not: two taps holding the same pixel then differed in the last bit (the later
+// one could win the window), and bn_apply_maxpool_kernel<AUX> (norm.hip: stem_aux_dot, the same statement, which it has always
+// compiled to) did not give this kernel's bits.
+template <int CE>
+__device__ __forceinline__ float aux_dot(const float* v, const float* w) {
+#pragma clang fp contract(off)
+    float d = 0.f;
+#pragma unroll
+    for (int e = 0; e < CE; ++e) d += v[e] * w[e];
+    return d;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void aux_fwd_kernel(const T* __restrict__ a1, const float* __restrict__ w, const float* __restrict__ bias,
                                                      const float* __restrict__ depth_feat, float* __restrict__ out, long ld_out,
@@ -35,9 +48,7 @@ __global__ __launch_bounds__(256) void aux_fwd_kernel(const T* __restrict__ a1, 
             const int ih = oh * 2 + (k >> 1), iw = ow * 2 + (k & 1);
             float v[CE];
             chunk_to_f<T>(*(const u32x4*)(a1 + (((long)b * H + ih) * W + iw) * 64 + sub * CE), v);
-            float d = 0.f;
-#pragma unroll
-            for (int e = 0; e < CE; ++e) d += v[e] * wv[e];
+            float d = aux_dot<CE>(v, wv);
 #pragma unroll
             for (int s = 1; s < LPP; s <<= 1) d += __shfl_xor(d, s);
             d += bv;

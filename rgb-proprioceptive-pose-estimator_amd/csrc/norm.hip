@@ -537,6 +537,15 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ 
 // the feature, the raw maximum and the winner tap exactly as aux_fwd_kernel does (same products of the ROUNDED a, same tie rule).
 // With `a` null the activated tensor is not written at all: nobody else reads it (the stem backward works from y), which saves its
 // 411-MB write here and the 411-MB read of the separate aux launch.
+// aux_fwd_kernel's aux_dot (heads.hip), word for word: no fused multiply-add, so that both kernels form the same sums bit for bit
+template <int CE>
+__device__ __forceinline__ float stem_aux_dot(const float* v, const float* w) {
+#pragma clang fp contract(off)
+    float d = 0.f;
+#pragma unroll
+    for (int e = 0; e < CE; ++e) d += v[e] * w[e];
+    return d;
+}
 struct StemAuxFwd {
     const float *w, *bias, *depth_feat;   // [64], [1], [B][Ho*Wo] or null
     float* out; long ld_out;              // feature columns of the fused feature rows
@@ -592,10 +601,7 @@ __global__ __launch_bounds__(256) void bn_apply_maxpool_kernel(const T* __restri
             }
             chunk_to_f<T>(packed, v);               // compare what the pool pass would have read back
             if (AUX && k / 3 >= 1 && k % 3 >= 1) {
-                float d = 0.f;
-#pragma unroll
-                for (int e = 0; e < CE; ++e) d += v[e] * aw[e];
-                ad[(k / 3 - 1) * 2 + (k % 3 - 1)] = d;
+                ad[(k / 3 - 1) * 2 + (k % 3 - 1)] = stem_aux_dot<CE>(v, aw);
             }
 #pragma unroll
             for (int e = 0; e < CE; ++e)
