@@ -338,7 +338,10 @@ int rpe_bn_apply_mask(int dtype, const void* y, const void* residual, void* out,
 int rpe_bn_apply_res_bn(int dtype, const void* y, const void* res_y, const float* res_scale, const float* res_shift, void* out, const float* scale,
                         const float* shift, long rows, int C, int relu, unsigned char* relu_mask, void* stream);
 /* dz = dA * (a_out > 0) (a_out null: no ReLU); dgamma, dbeta; dy = BN backward of dz; dz_out (nullable) = dz.
- * part: >= 2*1024*C floats of scratch; c1c2: 2*C floats of scratch; dpart: as for rpe_bn_finalize. */
+ * part: >= 2*1024*C floats of scratch; c1c2: 2*C floats of scratch; dpart: as for rpe_bn_finalize.
+ * C: with K = C / (16-byte chunk: 4 fp32, 8 16-bit elements), K <= 256 must divide 256 and K > 256 must be a multiple of 256
+ * (whole column slabs), C <= 4096; any other C is refused with RPE_ERR_SHAPE and nothing is written.  The same holds for
+ * rpe_bn_backward_reduce. */
 int rpe_bn_backward(int dtype, const void* dA, const void* a_out, const void* y, const float* mean, const float* invstd,
                     const float* gamma, float* dgamma, float* dbeta, void* dy, void* dz_out, long rows, int C, float* part,
                     long part_floats, float* c1c2, double* dpart, void* stream);

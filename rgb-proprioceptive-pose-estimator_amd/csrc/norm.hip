@@ -1136,6 +1136,8 @@ int bn_bwd_launch(const void* dA, const void* a_out, const void* y, const float*
     if (C % CE) return rpe_set_error(RPE_ERR_SHAPE, "bn_bwd: C must be a multiple of the 16-byte chunk");
     int SW = C < 256 * CE ? C : 256 * CE;
     if (256 % (SW / CE)) return rpe_set_error(RPE_ERR_SHAPE, "bn_bwd: C/chunk must divide 256");
+    // (C / SW used to truncate: C = 1536 in fp32 launched one slab and left channels 1024.. unreduced, their partial sums uninitialised)
+    if (C % SW) return rpe_set_error(RPE_ERR_SHAPE, "bn_bwd: C above 256 chunks must be a multiple of 256 chunks");
     const int slabs = C / SW;
     const int RPI = 256 / (SW / CE);
     long nb = (M + (long)RPI * 8 - 1) / ((long)RPI * 8);  // >= 8 iterations per block
