@@ -357,7 +357,12 @@ int rpe_bn_backward_from_dz(int dtype, const void* dz, const void* y, const floa
                             double* dpart, void* stream);
 
 /* ------------------------------------------------------------------ pooling */
-/* replaces: nn.MaxPool2d(3, 2, 1) of the ResNet stem; idx keeps the winning tap. */
+/* replaces: nn.MaxPool2d(3, 2, 1) of the ResNet stem; x [B][H][W][C] -> out, idx [B][(H-1)/2+1][(W-1)/2+1][C]; idx keeps the winning
+ * tap kh * 3 + kw (0..8) of each output element.  The rule is torch's max_pool2d: padding counts as -inf (never as 0); among equal
+ * values the first in-image tap in (kh, kw) order wins; a NaN beats everything and the LAST NaN of a window is named; a window whose
+ * in-image taps are all -inf names its first in-image tap (never a tap outside the image).
+ * B, H, W > 0 and C a positive multiple of the 16-byte chunk (4 fp32 / 8 16-bit elements), in the forward and the backward:
+ * anything else is refused with RPE_ERR_SHAPE before any launch and nothing is written. */
 int rpe_maxpool3x3s2_fwd(int dtype, const void* x, void* out, unsigned char* idx, int B, int H, int W, int C, void* stream);
 /* BatchNorm apply + ReLU and the 3x3 / stride 2 / pad 1 max pool behind it in one pass over the raw conv output y [B][H][W][C] (H, W even):
  * a = relu(y * scale + shift) [B][H][W][C], out = maxpool(a) [B][H/2][W/2][C], idx = winner taps -- bitwise what rpe_bn_apply followed by
@@ -368,6 +373,8 @@ int rpe_bn_apply_maxpool3x3s2(int dtype, const void* y, const float* scale, cons
 int rpe_bn_apply_maxpool3x3s2_aux(int dtype, const void* y, const float* scale, const float* shift, void* a, void* out, unsigned char* idx, int B, int H,
                                   int W, const float* aux_w, const float* aux_bias, const float* depth_feat, float* aux_out, long ld_aux_out, float* aux_raw,
                                   unsigned char* aux_idx, void* stream);
+/* dx [B][H][W][C] = (addend, or 0 when NULL) + the gradients dout of the windows whose idx names the pixel, summed in fp32 in
+ * ascending (kh, kw) order behind the addend and rounded once.  Shapes and refusals as for the forward. */
 int rpe_maxpool3x3s2_bwd(int dtype, const void* dout, const unsigned char* idx, const void* addend, void* dx, int B, int H, int W, int C,
                          void* stream);
 /* Stem backward in two passes over y (fused form of rpe_maxpool3x3s2_bwd + the aux head's scatter + rpe_bn_backward for the
@@ -381,7 +388,9 @@ int rpe_stem_bwd(int dtype, const void* dpool, const unsigned char* pool_idx, co
                  const float* invstd, const float* gamma, const float* aux_dout, long aux_ld, const float* aux_depth_feat,
                  const unsigned char* aux_idx, const float* aux_w, float* dgamma, float* dbeta, void* dy, int B, int H, int W, float* part,
                  long part_floats, float* c1c2, double* dpart, void* stream);
-/* replaces: nn.AdaptiveAvgPool2d((1,1)) + flatten; output fp32 [B][C] */
+/* replaces: nn.AdaptiveAvgPool2d((1,1)) + flatten; x [B][HW][C] -> output fp32 [B][C], and its backward dx = dout / HW.
+ * B, HW > 0 and C a positive multiple of the 16-byte chunk (4 fp32 / 8 16-bit elements): anything else is refused with
+ * RPE_ERR_SHAPE before any launch and nothing is written. */
 int rpe_avgpool_fwd(int dtype, const void* x, float* out, int B, int HW, int C, void* stream);
 int rpe_avgpool_bwd(int dtype, const float* dout, void* dx, int B, int HW, int C, void* stream);
 

@@ -505,8 +505,11 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const T* __restrict__ 
         const int b = (int)(pix / Ho);
         float best[CE];
         unsigned char bi[CE];
+        // a window whose in-image taps are all -inf names its FIRST IN-IMAGE tap, as torch does (tap 0 lies outside the image in the top row
+        // and left column: the backward would find no pixel that owns it).  Taps (1, 1) .. are always inside.
+        const unsigned char first = (unsigned char)((oh == 0 ? 3 : 0) + (ow == 0 ? 1 : 0));
 #pragma unroll
-        for (int e = 0; e < CE; ++e) { best[e] = -INFINITY; bi[e] = 0; }
+        for (int e = 0; e < CE; ++e) { best[e] = -INFINITY; bi[e] = first; }
         for (int kh = 0; kh < 3; ++kh) {
             const int ih = oh * 2 - 1 + kh;
             if (ih < 0 || ih >= H) continue;
@@ -1206,6 +1209,15 @@ int stem_bwd_launch(const void* dpool, const unsigned char* pidx, const StemAux&
     return 0;
 }
 
+// the pooling entry points' arguments: every extent positive and C a whole number of 16-byte chunks of the element type (C / chunk
+// truncates in the kernels: the call would return 0 having written some channels at the wrong stride).  0, or the error set.
+static int pool_args(int dtype, bool extents_ok, int C, const char* bad_dtype, const char* bad_shape) {
+    const int ce = dtype == RPE_F32 ? 4 : (dtype == RPE_BF16 || dtype == RPE_F16) ? 8 : 0;
+    if (!ce) return rpe_set_error(RPE_ERR_DTYPE, bad_dtype);
+    if (!extents_ok || C <= 0 || C % ce) return rpe_set_error(RPE_ERR_SHAPE, bad_shape);
+    return 0;
+}
+
 template <typename T> int bn_apply_dz_checked(const void* dz, const void* y, const float* mean, const float* invstd, const float* gamma,
                                                     const float* c1c2, void* dy, long rows, int C, hipStream_t s) {
     if (C % Elem<T>::kChunk) return rpe_set_error(RPE_ERR_SHAPE, "bn_backward_apply_dz: C must be a multiple of the 16-byte chunk");
@@ -1346,6 +1358,7 @@ int rpe_bn_backward_apply_dz(int dtype, const void* dz, const void* y, const flo
 }
 
 int rpe_maxpool3x3s2_fwd(int dtype, const void* x, void* out, unsigned char* idx, int B, int H, int W, int C, void* stream) {
+    if (int e = pool_args(dtype, B > 0 && H > 0 && W > 0, C, "maxpool: unsupported dtype", "maxpool: B, H, W positive, C a positive multiple of the 16-byte chunk")) return e;
     note_kernel("maxpool_fwd_kernel");
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     const long n = (long)B * Ho * Wo * C;
@@ -1395,6 +1408,7 @@ int rpe_bn_apply_maxpool3x3s2_aux(int dtype, const void* y, const float* scale, 
 
 int rpe_maxpool3x3s2_bwd(int dtype, const void* dout, const unsigned char* idx, const void* addend, void* dx, int B, int H, int W, int C,
                          void* stream) {
+    if (int e = pool_args(dtype, B > 0 && H > 0 && W > 0, C, "maxpool: unsupported dtype", "maxpool_bwd: B, H, W positive, C a positive multiple of the 16-byte chunk")) return e;
     note_kernel("maxpool_bwd_kernel");
     const int Ho = (H + 2 - 3) / 2 + 1, Wo = (W + 2 - 3) / 2 + 1;
     const long n = (long)B * H * W * C;
@@ -1407,6 +1421,7 @@ int rpe_maxpool3x3s2_bwd(int dtype, const void* dout, const unsigned char* idx, 
 }
 
 int rpe_avgpool_fwd(int dtype, const void* x, float* out, int B, int HW, int C, void* stream) {
+    if (int e = pool_args(dtype, B > 0 && HW > 0, C, "avgpool: unsupported dtype", "avgpool: B, HW positive, C a positive multiple of the 16-byte chunk")) return e;
     if ((long)B * C <= 65536 && HW >= 16) {   // fewer chunks than lanes on the chip: 8 lanes per chunk
         if (dtype == RPE_F32) hipLaunchKernelGGL((avgpool_fwd_few_kernel<float>), dim3(ceil_div((long)B * C / 4 * 8, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)x, out, B, HW, C);
         else if (dtype == RPE_BF16) hipLaunchKernelGGL((avgpool_fwd_few_kernel<bf16>), dim3(ceil_div((long)B * C / 8 * 8, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16*)x, out, B, HW, C);
@@ -1424,6 +1439,7 @@ int rpe_avgpool_fwd(int dtype, const void* x, float* out, int B, int HW, int C, 
 }
 
 int rpe_avgpool_bwd(int dtype, const float* dout, void* dx, int B, int HW, int C, void* stream) {
+    if (int e = pool_args(dtype, B > 0 && HW > 0, C, "avgpool: unsupported dtype", "avgpool_bwd: B, HW positive, C a positive multiple of the 16-byte chunk")) return e;
     const long n = (long)B * HW * C;
     if (dtype == RPE_F32) hipLaunchKernelGGL((avgpool_bwd_kernel<float>), dim3(ew_grid(n / 4)), dim3(256), 0, (hipStream_t)stream, dout, (float*)dx, B, HW, C);
     else if (dtype == RPE_BF16) hipLaunchKernelGGL((avgpool_bwd_kernel<bf16>), dim3(ew_grid(n / 8)), dim3(256), 0, (hipStream_t)stream, dout, (bf16*)dx, B, HW, C);
