@@ -604,6 +604,40 @@ int rpe_adamw_step_sched(float* p, const float* g, float* m, float* v, float* em
                          double weight_decay, double ema_decay, const float* state, const float* sched, int use_clip, void* stream);
 int rpe_swap_f32(float* a, float* b, long n, void* stream);
 
+/* replaces: the per-layer instruments one would write in torch after optimizer.step() -- torch._foreach_norm over the gradients and
+ * over the parameters, an isfinite count and a zero count per tensor, the update-to-weight ratio, and the .tolist() that brings them
+ * to the host (none of it is in the reference, whose loop logs epoch averages only): several launches per
+ * tensor (a ResNet-50 arena holds 161) and a host synchronisation that a captured train step cannot contain.  Here: two launches per
+ * param group, nothing read by the host, gated by the device's own step count.
+ * p, g, m, v: four fp32 arenas of one layout (parameters, gradients, Adam's moments), 16-byte aligned; none is written.
+ * table: T entries {offset, numel, first_row} of int64 on the device, in arena order.  Tensor t is elements [offset, offset + numel)
+ *     of every arena -- nothing outside these ranges is ever loaded, so padding lanes and frozen neighbours cannot reach a result --
+ *     and owns the rpe_param_stats_rows(numel) partial rows from first_row on.  rpe_param_stats_rows is a function of numel alone
+ *     (ceil(numel / a fixed chunk), at least 1; it needs no device), never of the device, so data-parallel ranks add in one order.
+ * param_stats: one workgroup per row writes RPE_PARAM_STATS_PART_COLS fp64 values to partials[row][..] with plain stores (fixed
+ *     reduction tree, no atomics).  Per element, everything widened to fp64 first: g^2, p^2, d^2 with d = (m / bc1) / (sqrt(v) /
+ *     sqrt(bc2) + eps), bc1 = 1 - beta1^t, bc2 = 1 - beta2^t, t = state[5] -- rpe_adamw_step_clip's direction of the update just
+ *     applied, in fp64; the non-finite counts of g and of p; the count of g == 0 (either sign); the maxima of |g| and |p|.  A
+ *     non-finite element is counted and left out of every sum and maximum; a non-finite d is left out of sum d^2.
+ * param_stats_finalize: one workgroup per tensor adds its rows in ascending order and writes out[t][0 .. RPE_PARAM_STATS_COLS), fp64:
+ *     0 sum g^2    1 sum p^2    2 sum d^2 (0 when state[3] != 0: a skipped fp16 step applied nothing)    3 max|g|    4 max|p|
+ *     5 non-finite elements of g    6 elements of g equal to 0    7 non-finite elements of p    8 stamp: state[5] of the step measured
+ *     9 the first step at which column 5 or 7 was non-zero: written only while it is 0, so it stays until the host zeroes it (0: never)
+ *     `out` must hold zeros (column 9 at least) before the first call.
+ * Gate: every >= 1.  When (long)state[5] % every != 0 every workgroup of both kernels returns at once, and partials and out keep
+ *     their contents bit for bit: a captured step launches at every replay and the device decides.
+ * Refused, nothing launched: T <= 0, a null pointer, every < 1 (RPE_ERR_SHAPE); an arena that is not 16-byte aligned or an offset that
+ *     is not a multiple of 4 floats (RPE_ERR_ALIGN); a negative offset or numel, or a first_row that is not the sum of the rows of the
+ *     entries before it (RPE_ERR_SHAPE).  The table is checked on the HOST side of this call, from `table_host`, a host copy of the
+ *     same 3 T integers passed alongside (the device table is not read back); the grid is the row total derived from it.  finalize
+ *     reads the device table only: run it after a param_stats call that accepted the same table. */
+#define RPE_PARAM_STATS_COLS 10
+#define RPE_PARAM_STATS_PART_COLS 8
+long rpe_param_stats_rows(long numel);
+int rpe_param_stats(const float* p, const float* g, const float* m, const float* v, const long* table, const long* table_host, int T,
+                    double* partials, double beta1, double beta2, double eps, const float* state, long every, void* stream);
+int rpe_param_stats_finalize(const double* partials, const long* table, int T, double* out, const float* state, long every, void* stream);
+
 /* ------------------------------------------------------------------ ResNet-50 trunk engine */
 /* One object = one (batch, dtype) plan for the whole torchvision-shaped ResNet-50 body:
  * stage image -> conv1/bn1/relu -> maxpool -> 16 bottlenecks -> avgpool -> fc, forward and

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("RPE_LIB_PATH") or os.path.join(_HERE, "librpe_hip.so"
 
 RPE_F32, RPE_BF16, RPE_F16 = 0, 1, 2
 ABI_VERSION = 3
+PARAM_STATS_COLS, PARAM_STATS_PART_COLS = 10, 8     # RPE_PARAM_STATS_COLS, RPE_PARAM_STATS_PART_COLS
 
 
 class RpeError(RuntimeError):
@@ -165,6 +166,9 @@ _SPEC = {
     "rpe_lr_schedule": (I, [P, I, L, D, L, D, L, D, P, P]),
     "rpe_adamw_step_sched": (I, [P, P, P, P, P, L, D, D, D, D, D, D, P, P, I, P]),
     "rpe_swap_f32": (I, [P, P, L, P]),
+    "rpe_param_stats_rows": (L, [L]),
+    "rpe_param_stats": (I, [P, P, P, P, P, P, I, P, D, D, D, P, L, P]),
+    "rpe_param_stats_finalize": (I, [P, P, I, P, P, L, P]),
     "rpe_resnet50_create": (I, [POINTER(c_void_p), I, I, I, I, I]),
     "rpe_resnet_create": (I, [POINTER(c_void_p), I, I, I, I, I, I]),
     "rpe_resnet50_destroy": (None, [P]),
@@ -213,7 +217,7 @@ _SPEC = {
     "rpe_saliency_overlay_u8": (I, [P, P, P, P, I, I, I, I, P, P]),
 }
 # entry points whose int return value is data, not a status
-_NOT_STATUS = {"rpe_abi_version", "rpe_conv2d_wgrad_halo_min_width", "rpe_grad_sumsq_rows"}
+_NOT_STATUS = {"rpe_abi_version", "rpe_conv2d_wgrad_halo_min_width", "rpe_grad_sumsq_rows", "rpe_param_stats_rows"}
 
 EXPORTS = tuple(_SPEC)
 

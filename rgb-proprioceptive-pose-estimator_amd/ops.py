@@ -11,7 +11,7 @@ import os
 
 import torch
 
-from ._lib import RPE_BF16, RPE_F16, RPE_F32, BnBwdEpilogue, ConvDesc, lib
+from ._lib import PARAM_STATS_COLS, PARAM_STATS_PART_COLS, RPE_BF16, RPE_F16, RPE_F32, BnBwdEpilogue, ConvDesc, lib
 
 _DT = {torch.float32: RPE_F32, torch.bfloat16: RPE_BF16, torch.float16: RPE_F16}
 
@@ -609,6 +609,68 @@ def error_stats(err):
 
 def adam_step(p, g, m, v, lr, beta1, beta2, eps, step):
     lib.rpe_adam_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, step, _stream())
+
+
+PARAM_STATS_COLUMNS = ("grad_sumsq", "weight_sumsq", "update_sumsq", "grad_max", "weight_max", "grad_nonfinite", "grad_zero", "weight_nonfinite",
+                       "step", "first_nonfinite_step")     # the columns of rpe_param_stats_finalize's `out`
+
+
+def param_stats_rows(n):
+    """partial rows tensor of `n` elements takes in rpe_param_stats: a function of n alone (needs no device)"""
+    return lib.rpe_param_stats_rows(int(n))
+
+
+def param_stats_table(entries):
+    """[(offset, numel)] in arena order -> the host copy of rpe_param_stats' table: int64 (T, 3) rows {offset, numel, first_row},
+    first_row the running sum of param_stats_rows(numel).  An offset that is no multiple of 4 floats is refused here as the C ABI
+    refuses it; move the result to the device with .to(device) and pass both."""
+    rows, tab = 0, []
+    for off, n in entries:
+        off, n = int(off), int(n)
+        if off < 0 or n < 0:
+            raise ValueError("param_stats_table: offset and numel must not be negative, got (%d, %d)" % (off, n))
+        if off % 4:
+            raise ValueError("param_stats_table: offset %d is not a multiple of 4 floats (16 bytes)" % off)
+        tab.append((off, n, rows))
+        rows += param_stats_rows(n)
+    if not tab:
+        raise ValueError("param_stats_table: no tensors")
+    return torch.tensor(tab, dtype=torch.int64)
+
+
+def param_stats_total_rows(table_host):
+    """rows of the partials buffer a table needs"""
+    return int(table_host[-1, 2]) + param_stats_rows(int(table_host[-1, 1]))
+
+
+def param_stats(p, g, m, v, table, table_host, partials, out, beta1, beta2, eps, state, every=1):
+    """Per-tensor statistics of four fp32 arenas of one layout (rpe_param_stats + rpe_param_stats_finalize: two launches, no host
+    synchronisation).  table / table_host: param_stats_table(...) on the device / on the host; partials: fp64 device buffer of at
+    least param_stats_total_rows x PARAM_STATS_PART_COLS; out: fp64 (T, PARAM_STATS_COLS) device tensor, columns PARAM_STATS_COLUMNS,
+    zeroed by the caller before the first call (column 9 is sticky); state: the optimizer's 8-float device state block (state[5] the
+    step count, state[3] the skip flag).  Nothing is written unless (long)state[5] % every == 0."""
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        if t.dtype != torch.float32 or t.numel() != p.numel():
+            raise ValueError("param_stats: %s must be fp32 with p's %d elements" % (name, p.numel()))
+        _chk(t, name)
+    if table_host.dtype != torch.int64 or table_host.is_cuda or table_host.dim() != 2 or table_host.shape[1] != 3 or table_host.shape[0] < 1:
+        raise ValueError("param_stats: table_host must be an int64 (T, 3) CPU tensor (param_stats_table)")
+    if table.dtype != torch.int64 or tuple(table.shape) != tuple(table_host.shape):
+        raise ValueError("param_stats: table must be table_host on the device")
+    T = table_host.shape[0]
+    if int((table_host[:, 0] + table_host[:, 1]).max()) > p.numel():
+        raise ValueError("param_stats: a tensor of the table ends behind the arena")
+    if partials.dtype != torch.float64 or partials.numel() < param_stats_total_rows(table_host) * PARAM_STATS_PART_COLS:
+        raise ValueError("param_stats: partials must be fp64 with %d rows of %d" % (param_stats_total_rows(table_host), PARAM_STATS_PART_COLS))
+    if out.dtype != torch.float64 or out.numel() != T * PARAM_STATS_COLS:
+        raise ValueError("param_stats: out must be fp64 (%d, %d)" % (T, PARAM_STATS_COLS))
+    if state.dtype != torch.float32 or state.numel() < 8:
+        raise ValueError("param_stats: state is the 8-float device state block")
+    _chk(table, "table"), _chk(table_host, "table_host"), _chk(partials, "partials"), _chk(out, "out")
+    s = _stream()
+    lib.rpe_param_stats(_p(p), _p(g), _p(m), _p(v), _p(table), ctypes.c_void_p(table_host.data_ptr()), T, _p(partials), beta1, beta2, eps, _p(state),
+                        int(every), s)
+    lib.rpe_param_stats_finalize(_p(partials), _p(table), T, _p(out), _p(state), int(every), s)
 
 
 def feature_planes(x_nhwc, image=None, out=None, minmax=None):

@@ -12,6 +12,9 @@ Three more, off by default and on the device as well: `lr_schedule` (LRSchedule:
 evaluated by rpe_lr_schedule from the device's step count), per-group hyper-parameters (every param group is updated with its own lr,
 betas, eps and weight_decay over its own arena segments) and `ema_decay` (an exponential moving average of the weights, written by the
 update kernel itself).  lr_factor() below is the one statement of the schedule rule.
+
+One instrument, off by default and on the device too: `telemetry=K` measures, every K-th optimizer step and after the update, per-tensor
+gradient / weight / update norms, maxima, non-finite and zero counts of every param group (rpe_param_stats: two launches per group).
 """
 import contextlib
 import math
@@ -19,7 +22,7 @@ import math
 import torch
 
 from . import ops
-from ._lib import lib
+from ._lib import PARAM_STATS_COLS, PARAM_STATS_PART_COLS, lib
 from .params import arena_of
 
 
@@ -107,7 +110,7 @@ def lr_factor(schedule, e):
 
 class FusedAdam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, capturable=False, *, weight_decay=0.0, max_grad_norm=None,
-                 lr_schedule=None, ema_decay=None):
+                 lr_schedule=None, ema_decay=None, telemetry=None):
         """capturable: keep the step count (for the bias corrections) on the DEVICE, so that a captured hipGraph of the whole
         train step (util.learn_utils.GraphedTrainStep) advances it at every replay; a host-side count would be frozen at its
         capture-time value.  Same update rule either way.
@@ -133,7 +136,25 @@ class FusedAdam(torch.optim.Optimizer):
         Neither is a param-group key: they are attributes, and top-level keys ("lr_schedule", "ema") of state_dict().  With either set
         the step count lives on the device as well.
         Param groups: every group is updated with its own lr, betas, eps and weight_decay over its own parameters' segments;
-        max_grad_norm is one global norm and must be the same in all groups."""
+        max_grad_norm is one global norm and must be the same in all groups.
+
+        telemetry: None (off) or a positive int K: after the update kernels of every param group, two more launches (rpe_param_stats,
+        rpe_param_stats_finalize) reduce that group's trainable tensors of p, g, m, v to one fp64 row each -- sum g^2, sum p^2, sum d^2
+        (d the Adam direction of the update just applied, with the group's betas and eps), max|g|, max|p|, non-finite g, zero g,
+        non-finite p, the step measured, the first step with a non-finite value (ops.PARAM_STATS_COLUMNS).  The device decides from its
+        own step count whether a step is measured (count % K == 0), so the launches are the same at every step and a captured train
+        step replays them; nothing is read by the host and nothing is allocated after the first step.  It sits after the update because
+        on the fp16 path the arena gradient carries the loss scale until this step's unscale pass, and because d needs the new moments.
+        A skipped fp16 step does not advance the count: it is measured again if the count is still a multiple of K, shows its non-finite
+        gradients, and reports sum d^2 = 0.  `param_stats` is the (T, COLS) device tensor (None before the first step), rows in the
+        order of param_stats_names(); reset_param_stats() clears the sticky column.  Not a state_dict key.  Like the other options it
+        keeps a step count on the device: the one the other options or `capturable` already keep, and without any of them a count of
+        its own, bumped by one extra launch behind update launches that stay exactly those of telemetry=None (the host-count and the
+        device-count update kernels round differently in the last bit; telemetry must not choose between them)."""
+        if telemetry is not None and not (_is_int(telemetry) and telemetry >= 1):
+            raise ValueError("invalid telemetry %r: None (off) or an integer >= 1 (measure every K-th step)" % (telemetry,))
+        self.telemetry = telemetry
+        self._tele = None           # (arena, per-group plans, out, the param group of every row): built at the first measured step
         if lr < 0.0 or eps < 0.0 or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
             raise ValueError("invalid Adam hyper-parameters")
         _check_options(weight_decay, max_grad_norm)
@@ -306,7 +327,68 @@ class FusedAdam(torch.optim.Optimizer):
                                             g["lr"], b1, b2, g["eps"], wd, ops._p(st), use_clip, s)
         if max_norm is not None:
             self._clip_state = st
+        self._measure(arena, groups, st)
         return None
+
+    def _measure(self, arena, groups, st):
+        """telemetry: after the update kernels, two launches per param group over that group's tensors, with its betas and eps"""
+        if self.telemetry is None:
+            return
+        for (g, _), plan in zip(groups, self._telemetry_plans(arena, groups)):
+            if plan is not None:
+                table, table_host, partials, out = plan
+                ops.param_stats(arena.flat, arena.grad, self._m, self._v, table, table_host, partials, out, g["betas"][0], g["betas"][1], g["eps"],
+                                st, self.telemetry)
+
+    def _telemetry_tensors(self, arena, group):
+        """the (parameter, arena offset) pairs a group's telemetry rows stand for: its trainable parameters in arena order"""
+        only = {id(p) for p in group["params"]}
+        return [(p, off) for p, off in zip(arena.params, arena.offsets) if p.requires_grad and id(p) in only]
+
+    def _telemetry_plans(self, arena, groups):
+        """per param group (table on the device, its host copy, partial rows, rows of `param_stats`), or None for a group without
+        trainable parameters; built once per arena"""
+        if self._tele is None or self._tele[0] is not arena:
+            dev = arena.flat.device
+            hosts = [[(off, p.numel()) for p, off in self._telemetry_tensors(arena, g)] for g, _ in groups]
+            hosts = [ops.param_stats_table(h) if h else None for h in hosts]
+            out = torch.zeros(sum(h.shape[0] for h in hosts if h is not None), PARAM_STATS_COLS, dtype=torch.float64, device=dev)
+            plans, row_group, t0 = [], [], 0
+            for k, h in enumerate(hosts):
+                if h is None:
+                    plans.append(None)
+                    continue
+                partials = torch.zeros(ops.param_stats_total_rows(h), PARAM_STATS_PART_COLS, dtype=torch.float64, device=dev)
+                plans.append((h.to(dev), h, partials, out[t0:t0 + h.shape[0]]))
+                row_group += [k] * h.shape[0]
+                t0 += h.shape[0]
+            self._tele = (arena, plans, out, row_group)
+        return self._tele[1]
+
+    @property
+    def param_stats(self):
+        """(T, PARAM_STATS_COLS) fp64 device tensor of the last measured step, columns ops.PARAM_STATS_COLUMNS, one row per trainable
+        tensor: param group by param group, arena order within a group (arena order overall when the groups do not interleave).  None
+        before the first step; reading it synchronises."""
+        return None if self._tele is None else self._tele[2]
+
+    def param_stats_names(self, model):
+        """the parameter names of `model` in the order of the rows of `param_stats`"""
+        params = [p for g in self.param_groups for p in g["params"]]
+        arena = self._arena if self._arena is not None else arena_of(params)
+        if arena is None:
+            raise RuntimeError("param_stats_names needs the model's flat parameter arena (run one forward on the device first)")
+        name_of = {id(p): n for n, p in model.named_parameters()}
+        return [name_of[id(p)] for g in self.param_groups for p, _ in self._telemetry_tensors(arena, g)]
+
+    def param_stats_groups(self):
+        """the index of the param group of every row of `param_stats` (None before the first step)"""
+        return None if self._tele is None else list(self._tele[3])
+
+    def reset_param_stats(self):
+        """zero the sticky column (the first step with a non-finite value) of every row"""
+        if self._tele is not None:
+            self._tele[2][:, 9].zero_()
 
     def _device_state(self, arena):
         # device-side step count: the same state block the loss scaler uses (amp.py), with scale 1 and no unscale pass
@@ -336,6 +418,7 @@ class FusedAdam(torch.optim.Optimizer):
                 for lo, hi in segs:
                     lib.rpe_adam_step_amp(ops._p(arena.flat[lo:hi]), ops._p(arena.grad[lo:hi]), ops._p(self._m[lo:hi]), ops._p(self._v[lo:hi]), hi - lo,
                                           g["lr"], b1, b2, g["eps"], ops._p(st), s)
+            self._measure(arena, groups, st)
             return None
         if self.capturable:
             st = self._device_state(arena)
@@ -346,11 +429,18 @@ class FusedAdam(torch.optim.Optimizer):
                 for lo, hi in segs:
                     lib.rpe_adam_step_amp(ops._p(arena.flat[lo:hi]), ops._p(arena.grad[lo:hi]), ops._p(self._m[lo:hi]), ops._p(self._v[lo:hi]), hi - lo,
                                           g["lr"], b1, b2, g["eps"], ops._p(st), s)
+            self._measure(arena, groups, st)
             return None
         for g, segs in groups:
             b1, b2 = g["betas"]
             for lo, hi in segs:
                 ops.adam_step(arena.flat[lo:hi], arena.grad[lo:hi], self._m[lo:hi], self._v[lo:hi], g["lr"], b1, b2, g["eps"], self._step)
+        if self.telemetry is not None:
+            # telemetry alone: the update launches above are today's, bit for bit; the gate and d's bias corrections read a device-side
+            # count, bumped by one launch here (it starts at the host's count, and equals it from then on: no step is ever skipped)
+            st = self._device_state(arena)
+            lib.rpe_amp_update(ops._p(st), 1.0, 1.0, 1 << 30, ops._stream())
+            self._measure(arena, groups, st)
         return None
 
     def state_dict(self):
@@ -404,6 +494,6 @@ class FusedAdamW(FusedAdam):
     """FusedAdam with torch.optim.AdamW's default decoupled weight decay of 1e-2 (what fine-tuning a pretrained trunk expects)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, capturable=False, *, weight_decay=1e-2, max_grad_norm=None,
-                 lr_schedule=None, ema_decay=None):
+                 lr_schedule=None, ema_decay=None, telemetry=None):
         super().__init__(params, lr=lr, betas=betas, eps=eps, capturable=capturable, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
-                         lr_schedule=lr_schedule, ema_decay=ema_decay)
+                         lr_schedule=lr_schedule, ema_decay=ema_decay, telemetry=telemetry)

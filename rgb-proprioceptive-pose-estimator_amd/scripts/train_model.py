@@ -79,6 +79,10 @@ def build_parser():
     p.add_argument("--trunk_lr_scale", type=float, default=None, help="train the ResNet trunk at lr times this, as a param group of its own (default: one group)")
     p.add_argument("--ema_decay", type=float, default=None,
                    help="keep an exponential moving average of the weights on the device, validate with it and save it as <checkpoint>.ema (default: off)")
+    p.add_argument("--telemetry", type=int, nargs="?", const=1, default=None, metavar="K",
+                   help="per-tensor gradient / weight / update norms, non-finite and zero counts, measured on the device every K-th optimizer "
+                        "step (K = 1 when given without a value) and logged once per epoch; needs --optimizer fused (default: off)")
+    p.add_argument("--telemetry_out", type=str, default=None, metavar="FILE.npz", help="with --telemetry: save the per-epoch tables and the parameter names")
     p.add_argument("--episodes_seed", type=int, default=1234, help="seed of the synthetic episode generator")
     p.add_argument("--no_save", action="store_true", help="do not write the best-validation checkpoint")
     p.add_argument("--episodes", type=str, default=None, metavar="FILE.npz",
@@ -217,7 +221,7 @@ def build_model(args, compute_dtype):
 
 
 SCHEDULE_FLAGS = ("lr_schedule", "warmup_steps", "warmup_start_factor", "lr_total_steps", "lr_min_factor", "lr_step_size", "lr_gamma")
-FUSED_ONLY_FLAGS = SCHEDULE_FLAGS + ("trunk_lr_scale", "ema_decay")
+FUSED_ONLY_FLAGS = SCHEDULE_FLAGS + ("trunk_lr_scale", "ema_decay", "telemetry")
 
 
 def build_schedule(args):
@@ -246,8 +250,10 @@ def build_optimizer(args, params):
         raise SystemExit("--max_grad_norm needs --optimizer fused: the on-device norm and clip live in FusedAdam.step (optim.py)")
     for flag in FUSED_ONLY_FLAGS:
         if getattr(args, flag, None) is not None and args.optimizer != "fused":
-            raise SystemExit("--%s needs --optimizer fused: the on-device schedule, the per-group update and the weight average live in "
-                             "FusedAdam.step (optim.py)" % flag)
+            raise SystemExit("--%s needs --optimizer fused: the on-device schedule, the per-group update, the weight average and the telemetry "
+                             "pass live in FusedAdam.step (optim.py)" % flag)
+    if getattr(args, "telemetry_out", None) is not None and getattr(args, "telemetry", None) is None:
+        raise SystemExit("--telemetry_out needs --telemetry")
     params = list(params)
     if params and isinstance(params[0], dict):
         params = [dict({k: v for k, v in g.items() if k != "lr_scale"}, **({"lr": args.lr * g["lr_scale"]} if "lr_scale" in g else {})) for g in params]
@@ -257,6 +263,8 @@ def build_optimizer(args, params):
         extra["lr_schedule"] = schedule
     if ema_decay is not None:
         extra["ema_decay"] = ema_decay
+    if getattr(args, "telemetry", None) is not None:
+        extra["telemetry"] = args.telemetry
     if args.optimizer == "fused":
         if args.weight_decay:
             return FusedAdamW(params, lr=args.lr, weight_decay=args.weight_decay, max_grad_norm=args.max_grad_norm, **extra)
@@ -308,10 +316,21 @@ def main(argv=None):
     params = {"camera_name": args.camera_name, "noise_scale": args.noise_scale}
     if rank == 0:
         print("Training...")
-    return train(model=model, dataset=dataset, criterion=criterion, optimizer=optimizer, num_epochs=args.n_epochs,
-                 num_train_episodes_per_epoch=args.n_train_episodes_per_epoch, num_val_episodes_per_epoch=args.n_val_episodes_per_epoch,
-                 params=params, device=device, save_model=not args.no_save, augment=build_augment(args, rank),
-                 measurement_noise=build_measurement_noise(args, rank), **sampling)
+    telemetry_log = [] if args.telemetry_out is not None else None
+    result = train(model=model, dataset=dataset, criterion=criterion, optimizer=optimizer, num_epochs=args.n_epochs,
+                   num_train_episodes_per_epoch=args.n_train_episodes_per_epoch, num_val_episodes_per_epoch=args.n_val_episodes_per_epoch,
+                   params=params, device=device, save_model=not args.no_save, augment=build_augment(args, rank),
+                   measurement_noise=build_measurement_noise(args, rank), telemetry=args.telemetry, telemetry_log=telemetry_log, **sampling)
+    if telemetry_log and rank == 0:
+        save_telemetry(args.telemetry_out, telemetry_log)
+    return result
+
+
+def save_telemetry(path, log):
+    """--telemetry_out: `names` (T,) and one (epochs, T) array per figure of util.learn_utils.telemetry_report"""
+    import numpy as np
+    names = list(log[0])
+    np.savez(path, names=np.array(names), **{k: np.array([[epoch[n][k] for n in names] for epoch in log], dtype=np.float64) for k in log[0][names[0]]})
 
 
 if __name__ == "__main__":

@@ -16,6 +16,7 @@ ResNet; models/losses.py:114-128 is the loss; util/learn_utils.py:152-184 the st
     rpe::pose_loss / pose_distance_loss             PoseDistanceLoss (raw three-value form / differentiable scalar)
     rpe::pose_errors                                its "val" branch per sample: position error, |angle| error, unit-quaternion pose
     rpe::adam_step                                  torch.optim.Adam's update of one flat fp32 tensor, in place
+    rpe::param_stats                                torch._foreach_norm over gradients and parameters, isfinite / zero counts and the update norm per tensor, two launches
     rpe::augment_frames_u8                          (no counterpart: the reference does not augment) jitter, noise and erasing of raw uint8 frames
     rpe::sample_windows / gather_rows               DataLoader(shuffle=True) over episode windows resident in HBM: the batch's index, and its rows
     rpe::measurement_noise                          x0 + sqrt(scale) * randn_like(x0) with the quaternion renormalised (util/data_utils.py:162-167), drawn on the device
@@ -33,7 +34,7 @@ __all__ = ["NAMES"]
 
 _NS = "rpe"
 NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step", "augment_frames_u8", "sample_windows", "gather_rows",
-         "measurement_noise", "occlude_grid_u8", "pose_displacement", "saliency_map", "saliency_overlay_u8")
+         "measurement_noise", "occlude_grid_u8", "pose_displacement", "saliency_map", "saliency_overlay_u8", "param_stats")
 
 
 def _ops():
@@ -185,6 +186,15 @@ def _(pred, truth, eps):
 @torch.library.custom_op(_NS + "::adam_step", mutates_args=("p", "m", "v"), device_types="cuda")
 def adam_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, lr: float, beta1: float, beta2: float, eps: float, step: int) -> None:
     _ops().adam_step(p, g, m, v, lr, beta1, beta2, eps, step)
+
+
+# ---- training telemetry --------------------------------------------------------------------------------------------------------
+@torch.library.custom_op(_NS + "::param_stats", mutates_args=("partials", "out"), device_types="cuda")
+def param_stats(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, table: torch.Tensor, table_host: torch.Tensor, partials: torch.Tensor,
+                out: torch.Tensor, beta1: float, beta2: float, eps: float, state: torch.Tensor, every: int) -> None:
+    """per-tensor statistics of the four fp32 arenas into out fp64 (T, 10), columns ops.PARAM_STATS_COLUMNS; table / table_host:
+    ops.param_stats_table(...) on the device / on the host; written only when (long)state[5] % every == 0"""
+    _ops().param_stats(p, g, m, v, table, table_host, partials, out, beta1, beta2, eps, state, every)
 
 
 # ---- frame augmentation --------------------------------------------------------------------------------------------------------

@@ -436,9 +436,47 @@ def evaluate_episodes(model, dataset, num_episodes, params, *, max_frames=256, n
     return EpisodeEvaluation(outputs, poses, pos, ori, stats, scales, truth=truth, measurements=meas)
 
 
+def _telemetry_host(optimizer):
+    """param_stats (row-major) followed by the schedule's factor (1 without a schedule), as one fp64 device vector"""
+    stats = optimizer.param_stats
+    if stats is None:
+        raise RuntimeError("telemetry: the optimizer has not measured yet (FusedAdam(telemetry=K), after the first step)")
+    f = optimizer.lr_factor
+    return torch.cat([stats.reshape(-1), torch.ones(1, dtype=torch.float64, device=stats.device) if f is None else f.double().reshape(1)])
+
+
+def telemetry_report(optimizer, model, host=None):
+    """The last measured step of FusedAdam(telemetry=K) per parameter name -> {name: {grad_norm, weight_norm, grad_max, weight_max,
+    zero_frac, nonfinite, first_nonfinite_step, update_ratio, step}}, in the order of optimizer.param_stats_names(model).  ONE
+    device-to-host copy (which synchronises); `host`: that copy when the caller already made it (train() folds it into the phase's
+    one read), a sequence of T * COLS + 1 numbers.
+    grad_norm / weight_norm: l2 norms over the tensor's finite elements; zero_frac: the share of gradient elements that are +-0 (a
+    dead tensor: 1); nonfinite: inf / NaN elements of the gradient plus those of the weights; first_nonfinite_step: the first
+    measured step that saw any (0: never; sticky until optimizer.reset_param_stats()); step: the optimizer step measured.
+    update_ratio = lr_eff ||d|| / ||p||, lr_eff the param group's lr times the schedule's factor of that step and d = m_hat / (sqrt(v_hat)
+    + eps) the Adam direction of the update just applied.  It is the ADAM TERM ONLY: with weight decay the step also shrinks p by
+    lr_eff weight_decay p, which is not included; a clipped step is (d is formed from the moments the clipped gradient went into).
+    A skipped fp16 step reports 0; a tensor of norm 0 reports inf (or NaN when nothing moved either)."""
+    from .._lib import PARAM_STATS_COLS
+    names = optimizer.param_stats_names(model)
+    if host is None:
+        host = _telemetry_host(optimizer).cpu()
+    host = np.asarray(host, dtype=np.float64)
+    table, factor = host[:-1].reshape(len(names), PARAM_STATS_COLS), float(host[-1])
+    numel = {n: p.numel() for n, p in model.named_parameters()}
+    report = {}
+    with np.errstate(divide="ignore", invalid="ignore"):
+        for name, row, k in zip(names, table, optimizer.param_stats_groups()):
+            lr_eff = optimizer.param_groups[k]["lr"] * factor
+            report[name] = dict(grad_norm=float(np.sqrt(row[0])), weight_norm=float(np.sqrt(row[1])), grad_max=float(row[3]), weight_max=float(row[4]),
+                                zero_frac=float(row[6] / max(1, numel[name])), nonfinite=int(row[5] + row[7]), first_nonfinite_step=int(row[9]),
+                                update_ratio=float(lr_eff * np.sqrt(row[2]) / np.sqrt(row[1])), step=int(row[8]))
+    return report
+
+
 def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_per_epoch, num_val_episodes_per_epoch, params, device,
           save_path='default', save_model=True, logging=True, *, save_optimizer=False, augment=None, batch_size=None, window_stride=None,
-          shuffle_seed=0, measurement_noise=None):
+          shuffle_seed=0, measurement_noise=None, telemetry=None, telemetry_log=None):
     """See the module docstring.  Returns (model with the best validation weights, best validation loss).
     save_optimizer (addition; the reference saves weights only): also write `<save_path>.optim` with the optimizer state of the
     best-validation epoch so that a run can be resumed (`optimizer.load_state_dict(torch.load(path))`).
@@ -457,7 +495,17 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
     steps * batch_size * S frames per rank.  The `val` phase is unchanged.  A dataset without `sampler` is a ValueError.
     measurement_noise (util.data_utils.MeasurementNoise): in the `train` phase the model is fed measurement_noise(x0), drawn on the
     device afresh at every step, in place of the dataset's x0bar (drawn on the host once per refresh); it needs the batch's x0 rows
-    only, so every dataset takes it.  The `val` phase keeps the dataset's measurements, and the dataset's own pool is not written."""
+    only, so every dataset takes it.  The `val` phase keeps the dataset's measurements, and the dataset's own pool is not written.
+    telemetry (None or K >= 1; needs FusedAdam(telemetry=K) with the same K): at the end of every `train` phase the optimizer's
+    per-tensor table of the last measured step is read WITH the phase's one host read (no synchronisation per step is added) and
+    written as Telemetry/grad_norm/<name>, Telemetry/update_ratio/<name>, Telemetry/zero_frac/<name>; when a tensor has seen
+    non-finite values, one line names the first one and its step.  telemetry_log: a list that receives every epoch's
+    telemetry_report(...).  The `val` phase is untouched."""
+    if telemetry is not None and getattr(optimizer, "telemetry", None) != telemetry:
+        raise ValueError("train(telemetry={!r}) needs an optimizer built with the same option (optim.FusedAdam(..., telemetry={!r})); got {} with telemetry={!r}".format(
+            telemetry, telemetry, type(optimizer).__name__, getattr(optimizer, "telemetry", None)))
+    if telemetry is None and telemetry_log is not None:
+        raise ValueError("train(telemetry_log=...) belongs to telemetry=K")
     if measurement_noise is not None:
         from .data_utils import MeasurementNoise
         if not isinstance(measurement_noise, MeasurementNoise):
@@ -545,7 +593,14 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
                 stats = [sums] + ([] if clip_sums is None else [clip_sums])
                 if phase == "train" and scheduled and optimizer.lr_factor is not None:
                     stats.append(optimizer.lr_factor.double().reshape(1))
+                measured = phase == "train" and telemetry is not None and optimizer.param_stats is not None
+                if measured:
+                    n_head = sum(s.numel() for s in stats)
+                    stats.append(_telemetry_host(optimizer))
                 tot = (sums if len(stats) == 1 else torch.cat(stats)).tolist()  # the one host synchronisation of the phase
+                tele = None
+                if measured:
+                    tot, tele = tot[:n_head], telemetry_report(optimizer, model, tot[n_head:])
                 denom = steps * batch_size * seq * world if sampled else horizon * num_episodes
                 epoch_loss, epoch_pos_err, epoch_ori_err = tot[0] / denom, tot[1] / denom, tot[2] / denom
                 if phase == "val" and has_ema and epoch_loss < best_err and save_model and rank == 0:
@@ -562,6 +617,16 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
                     writer.add_scalar("GradClipped/" + tag, tot[4] / clip_steps, epoch)
                 if cur_lr is not None:
                     writer.add_scalar("LR/" + tag, cur_lr, epoch)
+                for name, r in (tele or {}).items():
+                    for key in ("grad_norm", "update_ratio", "zero_frac"):
+                        writer.add_scalar("Telemetry/{}/{}".format(key, name), r[key], epoch)
+            if tele is not None:
+                if telemetry_log is not None:
+                    telemetry_log.append(tele)
+                bad = [(r["first_nonfinite_step"], name) for name, r in tele.items() if r["first_nonfinite_step"]]
+                if bad and logging and rank == 0:
+                    step, name = min(bad, key=lambda b: b[0])
+                    print("telemetry: non-finite values first seen in {} at optimizer step {} ({} tensors affected so far)".format(name, step, len(bad)))
             if logging and rank == 0:
                 print('{} Loss: {:.4f}, PosErr: {:.4f}, OriErr: {:.4f}. Time elapsed = {:.0f}m {:.0f}s'.format(
                     phase, epoch_loss, epoch_pos_err, epoch_ori_err, time_elapsed // 60, time_elapsed % 60)
