@@ -1,9 +1,11 @@
 """The engine keeps a few switches that select an OLDER, still-needed code path (each is also what some configuration takes by itself:
 fp32 engines have no packed ReLU mask, hooks on conv1 take the unfused stem backward, a missing slab workspace falls back to atomics,
-one-stream execution is what a stream without a second queue gets).  Those paths must stay CORRECT: each switch is read once per
-process, so every group gets one child process that runs golden train steps under it.  Children run one after the other (one GPU
-process at a time).  The rejected kernel-configuration experiments of rounds 1-2 (RPE_NT_*, RPE_TN_*, RPE_GRAM, RPE_FWD_SPLIT, ...) were
-removed in round 3 together with their template instantiations."""
+one-stream execution is what a stream without a second queue gets).  Those paths must stay CORRECT.  The switches are listed in
+INTEGRATION.md section 5 with the moment each is read: some when an engine is created, most once per process on first use, two at
+every call, and four by the Python package (at import or per call) -- so every group gets one child process that runs golden train
+steps under it.  The child also runs tests/test_gpu_launch_census.py, which holds the kernels it launches
+against the variant's entry of tests/golden/launch_census.json: a group whose names are mistyped or no longer read fails there
+instead of passing on the default path.  Children run one after the other (one GPU process at a time)."""
 import os
 import subprocess
 import sys
@@ -49,8 +51,8 @@ ENGINE_VARIANTS = [
 def test_engine_variant_parity(env):
     child_env = dict(os.environ)
     child_env.update(env)
-    cmd = [sys.executable, "-m", "pytest", os.path.join(HERE, "test_gpu_models.py"), "-q", "-x", "-p", "no:cacheprovider", "-k",
-           "(test_model_fp32_matches_reference_and_oracle and tdo_v2) or (test_model_bf16_tracks_fp32_reference and no)"]   # (fp32 golden step of a sequence model + the 16-bit path of the benchmarked model)
+    cmd = [sys.executable, "-m", "pytest", os.path.join(HERE, "test_gpu_models.py"), os.path.join(HERE, "test_gpu_launch_census.py"), "-q", "-x", "-p", "no:cacheprovider", "-k",
+           "(test_model_fp32_matches_reference_and_oracle and tdo_v2) or (test_model_bf16_tracks_fp32_reference and no) or test_launch_census"]   # (fp32 golden step of a sequence model + the 16-bit path of the benchmarked model)
     r = subprocess.run(cmd, env=child_env, cwd=os.path.dirname(HERE), capture_output=True, text=True, timeout=900)
     tail = (r.stdout or "")[-3000:] + (r.stderr or "")[-1000:]
     assert r.returncode == 0, "variant %r failed:\n%s" % (env, tail)
