@@ -103,6 +103,18 @@ typedef struct {
 long rpe_conv2d_dgrad_stats_tiles(const rpe_conv_desc* d, int dtype);
 int rpe_conv2d_dgrad_bn(const rpe_conv_desc* d, int dtype, const void* dy, const void* w_crsk, void* dz, const void* addend,
                         const rpe_bn_bwd_epilogue* bn, void* stream);
+/* Compact data gradient of a 1x1 / stride-2 / pad-0 conv with even in_h, in_w (a ResNet projection shortcut of layers 2-4; replaces the
+ * conv-transpose of downsample[0] in torchvision's Bottleneck, util/model_utils.py:136): such a conv reads the pixels (b, 2h', 2w') alone, so
+ *   dx_compact[B][in_h/2][in_w/2][in_c] = dy[B*Ho*Wo][out_c] * w_crsk^T      (one dense GEMM, no zero-filled full-resolution tensor)
+ * holds every non-zero row of rpe_conv2d_dgrad's dx.  Other shapes: RPE_ERR_SHAPE.
+ * The *_sub forms are rpe_conv2d_dgrad / rpe_conv2d_dgrad_bn / rpe_conv1x1_dgrad_kcat_y of a 1x1 / stride-1 conv with even in_h, in_w whose
+ * addend is such a compact tensor [B][in_h/2][in_w/2][in_c]: pixel (b, h, w) adds compact pixel (b, h/2, w/2) when h and w are even and
+ * +0 otherwise -- bitwise what the unchanged call returns for the same values scattered into a zero-filled full-resolution addend.
+ * With a BN epilogue the ReLU mask comes from bn->a_mask or bn->a_out; the other mask forms take no compact addend (RPE_ERR_SHAPE). */
+int rpe_conv1x1s2_dgrad_compact(const rpe_conv_desc* d, int dtype, const void* dy, const void* w_crsk, void* dx_compact, void* stream);
+int rpe_conv2d_dgrad_sub(const rpe_conv_desc* d, int dtype, const void* dy, const void* w_crsk, void* dx, const void* addend_compact, void* stream);
+int rpe_conv2d_dgrad_bn_sub(const rpe_conv_desc* d, int dtype, const void* dy, const void* w_crsk, void* dz, const void* addend_compact,
+                            const rpe_bn_bwd_epilogue* bn, void* stream);
 /* A bottleneck block WITHOUT its raw conv3 output (16-bit element types; replaces conv3 -> bn3 -> (+identity) -> ReLU of torchvision's
  * Bottleneck in training mode -- util/model_utils.py:136 builds it, models/naive.py:316 calls it -- and their backward).
  * BatchNorm statistics of a 1x1 conv follow from its INPUT: y = x W^T gives mean_c = w_c . colsum(x) / M, E[y_c^2] = w_c^T (x^T x) w_c / M.
@@ -150,6 +162,9 @@ int rpe_bn_bwd_fold_y_conv1x1(int dtype, int out_c, int in_c, const void* w_dgra
                               const float* c1c2, void* w_kcat, float* bias, void* stream);
 int rpe_conv1x1_dgrad_kcat_y(const rpe_conv_desc* d, int dtype, const void* dz, const void* y, const void* w_kcat, const float* bias, void* dx,
                              const void* addend, const rpe_bn_bwd_epilogue* bn, void* stream);
+/* (addend = a compact shortcut gradient: see rpe_conv1x1s2_dgrad_compact) */
+int rpe_conv1x1_dgrad_kcat_y_sub(const rpe_conv_desc* d, int dtype, const void* dz, const void* y, const void* w_kcat, const float* bias, void* dx,
+                                 const void* addend_compact, const rpe_bn_bwd_epilogue* bn, void* stream);
 long rpe_conv1x1_wgrad_folded_y_scratch_bytes(const rpe_conv_desc* d, int dtype);
 int rpe_conv1x1_wgrad_folded_y(const rpe_conv_desc* d, int dtype, const void* dz, const void* y, const void* x, const float* gamma, const float* invstd,
                                const float* mean, const float* c1c2, float* dw, void* scratch, long scratch_bytes, void* stream);

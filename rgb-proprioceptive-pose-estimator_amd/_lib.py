@@ -78,6 +78,10 @@ _SPEC = {
     "rpe_conv2d_dgrad_stats_tiles": (L, [PD, I]),
     "rpe_conv2d_fwd_stats_tiles": (L, [PD, I]),
     "rpe_conv2d_dgrad_bn": (I, [PD, I, P, P, P, P, POINTER(BnBwdEpilogue), P]),
+    "rpe_conv1x1s2_dgrad_compact": (I, [PD, I, P, P, P, P]),
+    "rpe_conv2d_dgrad_sub": (I, [PD, I, P, P, P, P, P]),
+    "rpe_conv2d_dgrad_bn_sub": (I, [PD, I, P, P, P, P, POINTER(BnBwdEpilogue), P]),
+    "rpe_conv1x1_dgrad_kcat_y_sub": (I, [PD, I, P, P, P, P, P, P, POINTER(BnBwdEpilogue), P]),
     "rpe_bn_backward_reduce": (I, [I, P, P, P, P, P, P, P, P, L, I, P, L, P, P, P]),
     "rpe_bn_backward_from_dz": (I, [I, P, P, P, P, P, P, I, P, P, P, L, I, P, P, P]),
     "rpe_bn_bwd_fold_scratch_bytes": (L, [I, I, I]),

@@ -86,9 +86,19 @@ static int conv_fwd_t(const rpe_conv_desc* d, const void* x, const void* w, void
     return launch_nt<T>(a, MODE_CONV, s);
 }
 
+// A 1x1 / stride-2 / pad-0 conv over even dims touches the input pixels (b, 2h', 2w') alone, and there its data gradient is the plain
+// product dy [B Ho Wo][out_c] * w [out_c][in_c]: the COMPACT form keeps just those rows ([B][H/2][W/2][in_c]) instead of a
+// full-resolution tensor that is three quarters zeros, and the data gradient it is added to reads it as a subsampled addend (NTArgs::add_sub).
+static inline bool s2_compact_ok(const rpe_conv_desc* d) {
+    return d->kh == 1 && d->kw == 1 && d->stride == 2 && d->pad == 0 && !(d->in_h & 1) && !(d->in_w & 1);
+}
+enum { DGRAD_FULL = 0, DGRAD_COMPACT_OUT = 1, DGRAD_SUB_ADDEND = 2 };
+
+// form: DGRAD_COMPACT_OUT -- dx is the compact gradient of a 1x1 / stride-2 conv (no addend, no BN epilogue);
+//       DGRAD_SUB_ADDEND  -- d is 1x1 / stride 1 with even dims and `addend` is such a compact tensor [B][H/2][W/2][in_c]
 template <typename T>
 static int conv_dgrad_t(const rpe_conv_desc* d, const void* dy, const void* w_crsk, void* dx, const void* addend, const rpe_bn_bwd_epilogue* bn,
-                        hipStream_t s) {
+                        hipStream_t s, int form = DGRAD_FULL) {
     const int Ho = out_dim(d->in_h, d->kh, d->stride, d->pad), Wo = out_dim(d->in_w, d->kw, d->stride, d->pad);
     NTArgs<T> a;
     memset(&a, 0, sizeof(a));
@@ -97,6 +107,16 @@ static int conv_dgrad_t(const rpe_conv_desc* d, const void* dy, const void* w_cr
     a.lda = d->out_c; a.ldb = a.K; a.ldc = d->in_c;
     a.addend = (const T*)addend; a.ld_add = d->in_c;
     a.role = 1;
+    if (form == DGRAD_COMPACT_OUT) {
+        if (!s2_compact_ok(d) || addend || bn) return rpe_set_error(RPE_ERR_SHAPE, "conv1x1s2_dgrad_compact: 1x1 / stride 2 / no padding with even in_h and in_w only");
+        a.M = d->batch * Ho * Wo;   // (Ho = in_h / 2, Wo = in_w / 2: the rows of dy)
+        return launch_nt<T>(a, MODE_DENSE, s);
+    }
+    if (form == DGRAD_SUB_ADDEND) {
+        if (!is_dense(d) || (d->in_h & 1) || (d->in_w & 1) || !addend)
+            return rpe_set_error(RPE_ERR_SHAPE, "conv2d_dgrad: a subsampled addend needs a 1x1 / stride-1 conv with even in_h and in_w");
+        a.add_sub = 1; a.add_H = d->in_h; a.add_W = d->in_w;
+    }
     if (bn) {
         // y == null with a_mask: the layer's raw output does not exist (y3-free bottleneck) -- mask from the bits, only sum dz is emitted
         const bool no_y = !bn->y && bn->a_mask;
@@ -595,7 +615,7 @@ static int bn_fold_y_t(int Co, int Ci, const void* wd, const float* gamma, const
 // fused BN-backward epilogue of the layer behind (the previous block's bn3: ReLU mask bits, partial sums)
 template <typename T>
 static int conv1x1_dgrad_kcat_y_t(const rpe_conv_desc* d, const void* dz, const void* y, const void* w_kcat, const float* bias, void* dx, const void* addend,
-                                  const rpe_bn_bwd_epilogue* bn, hipStream_t s) {
+                                  const rpe_bn_bwd_epilogue* bn, hipStream_t s, int sub_addend = 0) {
     NTArgs<T> a;
     memset(&a, 0, sizeof(a));
     a.A = (const T*)dz; a.A2 = (const T*)y; a.Bw = (const T*)w_kcat; a.C = (T*)dx;
@@ -604,6 +624,10 @@ static int conv1x1_dgrad_kcat_y_t(const rpe_conv_desc* d, const void* dz, const 
     a.bias = bias;
     a.addend = (const T*)addend; a.ld_add = d->in_c;
     a.role = 1;
+    if (sub_addend) {   // `addend` is the compact gradient of a 1x1 / stride-2 shortcut (conv_dgrad_t)
+        if ((d->in_h & 1) || (d->in_w & 1) || !addend) return rpe_set_error(RPE_ERR_SHAPE, "conv1x1_dgrad_kcat_y: a subsampled addend needs even in_h and in_w");
+        a.add_sub = 1; a.add_H = d->in_h; a.add_W = d->in_w;
+    }
     if (bn) {
         if (!bn->y || !bn->mean || !bn->invstd || !bn->stats_part) return rpe_set_error(RPE_ERR_SHAPE, "conv1x1_dgrad_kcat_y: y, mean, invstd, stats_part are required");
         a.bn_mode = bn->a_mask ? 4 : bn->a_out ? 1 : (bn->scale && bn->shift ? 2 : 3);
@@ -887,6 +911,24 @@ int rpe_conv2d_dgrad_bn(const rpe_conv_desc* d, int dtype, const void* dy, const
     DISPATCH(dtype, conv_dgrad_t, d, dy, w_crsk, dz, addend, bn, (hipStream_t)stream);
 }
 
+int rpe_conv1x1s2_dgrad_compact(const rpe_conv_desc* d, int dtype, const void* dy, const void* w_crsk, void* dx_compact, void* stream) {
+    if (int e = check_desc(d)) return e;
+    if (!dy || !w_crsk || !dx_compact) return rpe_set_error(RPE_ERR_SHAPE, "conv1x1s2_dgrad_compact: null argument");
+    DISPATCH(dtype, conv_dgrad_t, d, dy, w_crsk, dx_compact, nullptr, nullptr, (hipStream_t)stream, DGRAD_COMPACT_OUT);
+}
+
+int rpe_conv2d_dgrad_sub(const rpe_conv_desc* d, int dtype, const void* dy, const void* w_crsk, void* dx, const void* addend_compact, void* stream) {
+    if (int e = check_desc(d)) return e;
+    DISPATCH(dtype, conv_dgrad_t, d, dy, w_crsk, dx, addend_compact, nullptr, (hipStream_t)stream, DGRAD_SUB_ADDEND);
+}
+
+int rpe_conv2d_dgrad_bn_sub(const rpe_conv_desc* d, int dtype, const void* dy, const void* w_crsk, void* dz, const void* addend_compact,
+                            const rpe_bn_bwd_epilogue* bn, void* stream) {
+    if (int e = check_desc(d)) return e;
+    if (!bn) return rpe_set_error(RPE_ERR_SHAPE, "conv2d_dgrad_bn: null epilogue descriptor");
+    DISPATCH(dtype, conv_dgrad_t, d, dy, w_crsk, dz, addend_compact, bn, (hipStream_t)stream, DGRAD_SUB_ADDEND);
+}
+
 long rpe_bn_bwd_fold_scratch_bytes(int dtype, int out_c, int in_c) {
     long bytes = 0;
     int rc;
@@ -938,6 +980,14 @@ int rpe_conv1x1_dgrad_kcat_y(const rpe_conv_desc* d, int dtype, const void* dz, 
     if (d->kh != 1 || d->kw != 1 || d->stride != 1 || d->pad != 0) return rpe_set_error(RPE_ERR_SHAPE, "conv1x1_dgrad_kcat_y: 1x1 / stride 1 / no padding only");
     if (!dz || !y || !w_kcat || !bias || !dx || (d->out_c % 64)) return rpe_set_error(RPE_ERR_SHAPE, "conv1x1_dgrad_kcat_y: bad arguments (out_c % 64 == 0)");
     DISPATCH(dtype, conv1x1_dgrad_kcat_y_t, d, dz, y, w_kcat, bias, dx, addend, bn, (hipStream_t)stream);
+}
+
+int rpe_conv1x1_dgrad_kcat_y_sub(const rpe_conv_desc* d, int dtype, const void* dz, const void* y, const void* w_kcat, const float* bias, void* dx,
+                                 const void* addend_compact, const rpe_bn_bwd_epilogue* bn, void* stream) {
+    if (int e = check_desc(d)) return e;
+    if (d->kh != 1 || d->kw != 1 || d->stride != 1 || d->pad != 0) return rpe_set_error(RPE_ERR_SHAPE, "conv1x1_dgrad_kcat_y: 1x1 / stride 1 / no padding only");
+    if (!dz || !y || !w_kcat || !bias || !dx || (d->out_c % 64)) return rpe_set_error(RPE_ERR_SHAPE, "conv1x1_dgrad_kcat_y: bad arguments (out_c % 64 == 0)");
+    DISPATCH(dtype, conv1x1_dgrad_kcat_y_t, d, dz, y, w_kcat, bias, dx, addend_compact, bn, (hipStream_t)stream, 1);
 }
 
 static int wfold_y_dispatch(const rpe_conv_desc* d, int dtype, const void* dz, const void* y, const void* x, const float* gamma, const float* invstd,

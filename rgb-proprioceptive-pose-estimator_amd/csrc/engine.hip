@@ -979,7 +979,8 @@ static int bn_back(rpe_resnet50* e, ConvL& c, const void* dA, int relu, void* dy
 // data gradient of conv `c` with the BN-backward reduction of layer `bnl` (the layer producing c's input) fused in.
 // mask_mode 1: ReLU mask from bnl.a (residual block output); 2: mask recomputed from bnl.y, scale, shift.
 static int dgrad_fused(rpe_resnet50* e, ConvL& c, const void* dy, void* dz, const void* addend, ConvL* bnl, int mask_mode, void* stream,
-                       const unsigned char* relu_mask = nullptr, bool no_y = false, const void* t_a = nullptr, int t_p = 0, float* t_out = nullptr) {
+                       const unsigned char* relu_mask = nullptr, bool no_y = false, const void* t_a = nullptr, int t_p = 0, float* t_out = nullptr,
+                       bool sub_addend = false) {
     rpe_bn_bwd_epilogue ep;
     ep.y = no_y ? nullptr : bnl->y;                      // (y3-free block: sum dz only, rpe_conv2d_dgrad_bn)
     ep.a_mask = mask_mode == 1 ? relu_mask : nullptr;   // block outputs: 1 bit per element instead of re-reading a_out
@@ -990,7 +991,9 @@ static int dgrad_fused(rpe_resnet50* e, ConvL& c, const void* dy, void* dz, cons
     ep.stats_part = e->stats_part;
     e->pending_flops = conv_flops(c);
     // reads dy; writes dz; the fused epilogue also reads y (and a_out for residual outputs) and the shortcut addend
-    e->pending_bytes = conv_out_bytes(e, c) + conv_in_bytes(e, c) * ((no_y ? 1.0 : 2.0) + (mask_mode == 1 ? (ep.a_mask ? 1.0 / 16 : 1.0) : 0.0) + (addend ? 1.0 : 0.0));
+    // (sub_addend: the addend is the compact gradient of a stride-2 shortcut, a quarter of the rows)
+    e->pending_bytes = conv_out_bytes(e, c) + conv_in_bytes(e, c) * ((no_y ? 1.0 : 2.0) + (mask_mode == 1 ? (ep.a_mask ? 1.0 / 16 : 1.0) : 0.0) +
+                                                                      (addend ? (sub_addend ? 0.25 : 1.0) : 0.0));
     e->fused_tiles = (int)rpe_conv2d_dgrad_stats_tiles(&c.d, e->dtype);  // partial-sum rows this launch leaves behind
     if (t_out) {   // ... and T = dz^T a2 of the producing block from the tile on its way out (persistent launch)
         e->pending_flops += 2.0 * (double)c.rows * c.d.in_c * t_p;
@@ -998,7 +1001,8 @@ static int dgrad_fused(rpe_resnet50* e, ConvL& c, const void* dy, void* dz, cons
         PROF(e, RPE_PROF_CONV_DGRAD, stream, rpe_conv1x1_dgrad_bn_t(&c.d, e->dtype, dy, c.wd, dz, addend, &ep, t_a, t_p, t_out, e->main_slab, e->main_slab_bytes, stream));
         return 0;
     }
-    PROF(e, RPE_PROF_CONV_DGRAD, stream, rpe_conv2d_dgrad_bn(&c.d, e->dtype, dy, c.wd, dz, addend, &ep, stream));
+    if (sub_addend) PROF(e, RPE_PROF_CONV_DGRAD, stream, rpe_conv2d_dgrad_bn_sub(&c.d, e->dtype, dy, c.wd, dz, addend, &ep, stream));
+    else PROF(e, RPE_PROF_CONV_DGRAD, stream, rpe_conv2d_dgrad_bn(&c.d, e->dtype, dy, c.wd, dz, addend, &ep, stream));
     return 0;
 }
 
@@ -1153,6 +1157,16 @@ extern "C" int rpe_resnet50_backward_begin(rpe_resnet50_t* e, const float* d_fea
     return 0;
 }
 
+// workgroups of the zero-filled stride-2 shortcut data gradient from which the compact form is used: one per CU of the device
+static long compact_min_tiles() {
+    static const long cus = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) { (void)hipGetLastError(); n = 256; }
+        return (long)n;
+    }();
+    return cus;
+}
+
 // Backward through the next `count` bottleneck blocks (descending).  On return every gradient of those blocks is complete
 // in stream order on `stream` (the side stream is joined), so the caller may start reducing them across replicas.
 // Per block, entering with gA = dz3 (ReLU-masked gradient at the block output; for the last block: the raw dA).
@@ -1242,10 +1256,29 @@ extern "C" int rpe_resnet50_backward_blocks(rpe_resnet50_t* e, int count, int jo
             TRY(bn_from_dz(e, c1, c1.dy, c1.dy, stream));
             TRY(wgrad(e, c1, x_in, c1.dy, stream));
         }
+        // the previous block's dz3^T a2 rides on this block's conv1 data gradient (RPE_T_FUSE=1: decided here, the shortcut's form depends on it)
+        bool t_here = false;
+        if (!fold_c1 && bi > 0) {
+            const Block& pb = e->blocks[bi - 1];
+            const ConvL& p3 = e->convs[pb.c3];
+            t_here = pb.gram && pb.relu_mask && !e->y3_keep && e->t_fused && (p3.d.in_c == 64 || p3.d.in_c == 128) && (c1.d.in_c % 128) == 0 && c1.d.kh == 1 &&
+                     c1.d.stride == 1;
+        }
         const void* shortcut = gA;
+        // 1x1 / stride-2 projection shortcut over even dims (the entry blocks of layers 2-4): its data gradient lives on the even pixels alone.
+        // It is kept COMPACT ([B][H/2][W/2][C] in G[0]: one dense GEMM) and conv1's data gradient below reads it as a subsampled addend,
+        // instead of a full-resolution tensor that is three quarters zeros written once and read once.  A hooked layer output (its gradient
+        // joins here at full resolution), odd dims and the T side product keep the zero-filled form.  So do small launches: while the
+        // zero-filled launch -- 4 parity classes x 128-row tiles x 128-column tiles -- has fewer workgroups than the chip has CUs, its
+        // empty tiles run BESIDE the others in one round and the few MB it writes are read back from cache: there is nothing to take away,
+        // and the launch plan of such steps stays what it was (compact_min_tiles).
+        bool sub_addend = false;
         if (b.cd >= 0) {
             ConvL& cd = e->convs[b.cd];
             shortcut = e->G[0];
+            const long zero_filled_tiles = 4L * (((long)cd.d.batch * (cd.d.in_h / 2) * (cd.d.in_w / 2) + 127) / 128) * ((cd.d.in_c + 127) / 128);
+            sub_addend = zero_filled_tiles >= compact_min_tiles() && !hook_in && !t_here && cd.d.kh == 1 && cd.d.kw == 1 && cd.d.stride == 2 && cd.d.pad == 0 && !(cd.d.in_h & 1) && !(cd.d.in_w & 1) &&
+                         c1.d.kh == 1 && c1.d.kw == 1 && c1.d.stride == 1 && c1.d.pad == 0;
             if (ds_fold_ok && e->fold && e->train_mode && e->fold_w && e->wfold_scratch && !hook_in && cd.d.kh == 1 && cd.d.stride == 1 &&
                        cd.d.pad == 0 && cd.d.in_c <= e->fold_w_max && (cd.d.out_c % 128) == 0 && (cd.d.in_c % 64) == 0) {
                 // stride-1 projection shortcut (layer1): its BatchNorm backward folds into the 1x1 conv like conv3's -- one reduction pass
@@ -1274,7 +1307,14 @@ extern "C" int rpe_resnet50_backward_blocks(rpe_resnet50_t* e, int count, int jo
             } else {
                 TRY(bn_back(e, cd, gA, 0, cd.dy, nullptr, stream));          // no ReLU on the projection shortcut
                 TRY(wgrad(e, cd, x_in, cd.dy, stream));
-                PROF(e, RPE_PROF_CONV_DGRAD, stream, rpe_conv2d_dgrad(&cd.d, e->dtype, cd.dy, cd.wd, e->G[0], hook_in, stream));
+                e->pending_flops = conv_flops(cd);
+                if (sub_addend) {
+                    e->pending_bytes = conv_out_bytes(e, cd) + conv_in_bytes(e, cd) * 0.25;   // dy -> the even pixels of dx
+                    PROF(e, RPE_PROF_CONV_DGRAD, stream, rpe_conv1x1s2_dgrad_compact(&cd.d, e->dtype, cd.dy, cd.wd, e->G[0], stream));
+                } else {
+                    e->pending_bytes = conv_out_bytes(e, cd) + conv_in_bytes(e, cd) * (hook_in ? 2.0 : 1.0);
+                    PROF(e, RPE_PROF_CONV_DGRAD, stream, rpe_conv2d_dgrad(&cd.d, e->dtype, cd.dy, cd.wd, e->G[0], hook_in, stream));
+                }
             }
         }
         static const bool use_mask = getenv("RPE_NO_RELU_MASK") == nullptr;
@@ -1295,18 +1335,20 @@ extern "C" int rpe_resnet50_backward_blocks(rpe_resnet50_t* e, int count, int jo
                 extra = 1.0 + (mk ? 1.0 / 16 : 1.0);
             }
             e->pending_flops = conv_flops(c1) * 2.0;
-            e->pending_bytes = 2.0 * conv_out_bytes(e, c1) + conv_in_bytes(e, c1) * (2.0 + extra);   // dz1, y1; out, shortcut (, y3, mask)
+            e->pending_bytes = 2.0 * conv_out_bytes(e, c1) + conv_in_bytes(e, c1) * ((sub_addend ? 1.25 : 2.0) + extra);   // dz1, y1; out, shortcut (, y3, mask)
             e->fused_tiles = (int)rpe_conv2d_dgrad_stats_tiles(&c1.d, e->dtype);
-            PROF(e, RPE_PROF_CONV_DGRAD, stream, rpe_conv1x1_dgrad_kcat_y(&c1.d, e->dtype, c1.dy, c1.y, e->w_kcat, e->fold_bias, gD, shortcut, epp, stream));
+            if (sub_addend) PROF(e, RPE_PROF_CONV_DGRAD, stream, rpe_conv1x1_dgrad_kcat_y_sub(&c1.d, e->dtype, c1.dy, c1.y, e->w_kcat, e->fold_bias, gD, shortcut, epp, stream));
+            else PROF(e, RPE_PROF_CONV_DGRAD, stream, rpe_conv1x1_dgrad_kcat_y(&c1.d, e->dtype, c1.dy, c1.y, e->w_kcat, e->fold_bias, gD, shortcut, epp, stream));
         } else
         if (bi > 0) {
             const Block& pb = e->blocks[bi - 1];
             const bool pb_y3f = pb.gram && pb.relu_mask && !e->y3_keep;
             const ConvL& p3 = e->convs[pb.c3];
-            const bool t_here = pb_y3f && e->t_fused && (p3.d.in_c == 64 || p3.d.in_c == 128) && (c1.d.in_c % 128) == 0 && c1.d.kh == 1 && c1.d.stride == 1;
             e->blocks[bi - 1].t_ready = t_here;
             TRY(dgrad_fused(e, c1, c1.dy, gD, shortcut, &e->convs[pb.c3], 1, stream, use_mask ? pb.relu_mask : nullptr, pb_y3f,
-                            t_here ? e->convs[pb.c2].a : nullptr, p3.d.in_c, t_here ? pb.dzt_a : nullptr));   // dz3 of the previous block (+ its dz3^T a2)
+                            t_here ? e->convs[pb.c2].a : nullptr, p3.d.in_c, t_here ? pb.dzt_a : nullptr, sub_addend));   // dz3 of the previous block (+ its dz3^T a2)
+        } else if (sub_addend) {
+            PROF(e, RPE_PROF_CONV_DGRAD, stream, rpe_conv2d_dgrad_sub(&c1.d, e->dtype, c1.dy, c1.wd, gD, shortcut, stream));
         } else {
             PROF(e, RPE_PROF_CONV_DGRAD, stream, rpe_conv2d_dgrad(&c1.d, e->dtype, c1.dy, c1.wd, gD, shortcut, stream));
         }

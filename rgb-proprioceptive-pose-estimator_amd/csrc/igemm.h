@@ -128,6 +128,13 @@ template <typename T> struct NTArgs {
     float* slab;
     long slab_bytes;
     int splits, split_steps;
+    // Subsampled addend (NTArgs::addend; dense data-gradient role only): the output rows are the pixels [B][add_H][add_W] (both even) and the addend is the
+    // COMPACT tensor [B][add_H/2][add_W/2][ld_add] holding the even pixels alone -- the data gradient of a 1x1 / stride-2 shortcut
+    // (rpe_conv1x1s2_dgrad_compact).  Row m = (b, h, w) reads compact row (b*(add_H/2) + h/2)*(add_W/2) + w/2 and counts it as zero unless
+    // h and w are both even: every address lies inside the compact tensor, so the load needs no branch.  Launched as the SUB
+    // instantiation of nt_kernel; the fields sit at the end so that every other kernel reads its arguments where it always did.
+    int add_sub, add_H, add_W;
+    FastDiv add_div_hw, add_div_w;   // add_H * add_W, add_W
 };
 
 // split plan of an inference-forward launch with 64 x 64 tiles and K steps of `bk` elements: number of splits (1 = not

@@ -49,6 +49,14 @@ template <typename T> int launch_nt(NTArgs<T>& a, int mode, hipStream_t s) {
             (a.bn_mode && ((((uintptr_t)a.bn_y) & 15) || (a.bn_a && (((uintptr_t)a.bn_a) & 15)))))
             return rpe_set_error(RPE_ERR_ALIGN, "igemm_nt: conv outputs need N % 8 == 0 and 16-byte aligned rows");
     }
+    if (a.add_sub) {
+        // compact addend: the kernel maps output row m to a row of [B][add_H/2][add_W/2], which lies inside that tensor only if the
+        // rows ARE the pixels [B][add_H][add_W] with even dims
+        if (mode != MODE_DENSE || a.role != 1 || a.bn_mode == 6 || a.bn_mode == 7 || !a.addend || a.add_H <= 0 || a.add_W <= 0 || (a.add_H & 1) || (a.add_W & 1) ||
+            (a.M % ((long)a.add_H * a.add_W)))
+            return rpe_set_error(RPE_ERR_SHAPE, "igemm_nt: a subsampled addend needs a dense data gradient over [B][H][W] rows with even H and W");
+        a.add_div_hw = make_fastdiv((unsigned)(a.add_H * a.add_W)); a.add_div_w = make_fastdiv((unsigned)a.add_W);
+    }
     if (mode == MODE_STEM) return launch_nt_mode<T, MODE_STEM>(a, s);
     if (mode == MODE_DENSE) return launch_nt_mode<T, MODE_DENSE>(a, s);
     if (mode == MODE_HALO) {

@@ -102,7 +102,9 @@ __device__ __forceinline__ void dma16_asm(const __amdgpu_buffer_rsrc_t rs, unsig
 // VGPRs -- one workgroup per CU, 25 % slower)
 // Measured and rejected in rounds 1-2, code removed in round 3: 256-row / 8-wave tiles, 8 waves on the 128 x 128
 // tile, 128 x 256 / 8-wave tiles, non-temporal epilogue stores, 4- and 5-slot rings.
-template <typename T, int WAVES_M, int BN, int KCH, int MODE, int NST, int ROLE, int BNM = 0>
+// SUB: the addend is a compact (subsampled) tensor, NTArgs::add_sub -- a template parameter because the row arithmetic it needs at every
+// epilogue step grew the epilogue of EVERY dense data gradient by 12 % of its instructions when it was selected at run time.
+template <typename T, int WAVES_M, int BN, int KCH, int MODE, int NST, int ROLE, int BNM = 0, bool SUB = false>
 __global__ __launch_bounds__(128 * WAVES_M, 2) void nt_kernel(const NTArgs<T> p) {
     constexpr int WAVES_N = 2;   // waves along N: 64 x BN/2 per wave
     constexpr int CE = Elem<T>::kChunk, BK = KCH * CE;
@@ -393,13 +395,38 @@ __global__ __launch_bounds__(128 * WAVES_M, 2) void nt_kernel(const NTArgs<T> p)
     constexpr int kDepthHere = (ROLE == 5 || (ROLE == 1 && BNM == 5)) ? kEpiDepthLean : kEpiDepth;
     constexpr int DEPTH = PIPE ? (NSTEP < kDepthHere ? NSTEP : kDepthHere) : 1;
     u32x4 qd[DEPTH], qy[DEPTH], qa[DEPTH];
+    // Subsampled addend (NTArgs::add_sub, SUB kernels; dense data gradients): the addend row of output row m = (b, h, w) is the compact row of
+    // pixel (b, h/2, w/2), and `keep` tells whether the value counts (h, w both even) -- applied as a select where the value is used, so the
+    // load itself stays unconditional (a load under a per-lane branch makes the compiler drain the prefetch at every step, DESIGN.md
+    // section 0).  One bit of qkeep per prefetch slot.
+    constexpr bool SUBADD = SUB;
+    static_assert(!SUB || (ROLE == 1 && MODE == MODE_DENSE && !TFUSE), "subsampled addend: dense data gradients without the T side product");
+    unsigned qkeep = ~0u;
+    auto add_row = [&](long m, bool& keep) -> long {
+        if constexpr (SUBADD) {
+            const unsigned um = (unsigned)m;
+            const unsigned b = fd_div(um, p.add_div_hw);
+            const unsigned rem = um - b * p.add_div_hw.d;
+            const unsigned h = fd_div(rem, p.add_div_w);
+            const unsigned w = rem - h * p.add_div_w.d;
+            keep = !((h | w) & 1u);
+            return (long)((b * ((unsigned)p.add_H >> 1) + (h >> 1)) * ((unsigned)p.add_W >> 1) + (w >> 1));
+        } else {
+            keep = true;
+            return m;
+        }
+    };
     auto step_row = [&](int t) -> long { return out_row(wave_m * WM + (t / NPASS) * 16 + (t % NPASS) * RPP + erow); };
     auto issue = [&](int t) {
         if (!PIPE) return;
         const long m = step_row(t);
         const int sl = t % DEPTH;
         if (m < 0 || !ncol_ok) return;
-        if (vec_add) qd[sl] = ld16(e_addend + m * p.ld_add + n);
+        if (vec_add) {
+            bool keep;
+            qd[sl] = ld16(e_addend + add_row(m, keep) * p.ld_add + n);
+            if constexpr (SUBADD) qkeep = keep ? (qkeep | (1u << sl)) : (qkeep & ~(1u << sl));
+        }
         if (bn_mode && vec_c) {
             if (bn_mode != 5) qy[sl] = ld16(p.bn_y + m * p.ldc + n);
             if (bn_mode == 1) qa[sl] = ld16(p.bn_a + m * p.ldc + n);
@@ -705,8 +732,22 @@ __global__ __launch_bounds__(128 * WAVES_M, 2) void nt_kernel(const NTArgs<T> p)
                     // (PIPE roles move whole chunks: inside the m / ncol_ok guard vec_add and vec_c hold, so the prefetched registers are THE
                     // operands.  With the run-time fallback `else load8(..)` compiled beside them the wait in front of the first use had to cover a
                     // load that might just have been issued: vmcnt(0) in every step, which drained the whole prefetch -- round 4, from the ISA.)
-                    if constexpr (PIPE) chunk_to_f<T>(qd[sl], ad);
-                    else load8(e_addend, m * p.ld_add + n, vec_add, ad);
+                    if constexpr (PIPE) {
+                        u32x4 q = qd[sl];
+                        if constexpr (SUBADD) {   // (the zero bit pattern is +0 in every element type)
+                            const bool keep = (qkeep >> sl) & 1u;
+                            q.x = keep ? q.x : 0u; q.y = keep ? q.y : 0u; q.z = keep ? q.z : 0u; q.w = keep ? q.w : 0u;
+                        }
+                        chunk_to_f<T>(q, ad);
+                    } else {
+                        bool keep;
+                        const long ma = add_row(m, keep);
+                        load8(e_addend, ma * p.ld_add + n, vec_add, ad);
+                        if constexpr (SUBADD) {
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) ad[j] = keep ? ad[j] : 0.f;
+                        }
+                    }
 #pragma unroll
                     for (int j = 0; j < 8; ++j) v[j] += ad[j];
                 }
@@ -1302,8 +1343,31 @@ template <typename T, int MODE> static int launch_nt_split(NTArgs<T>& a, hipStre
 // -----------------------------------------------------------------------------------------------
 
 template <typename T, int WAVES_M, int BN, int KCH, int MODE, int NST, int ROLE> static int launch_nt_role(NTArgs<T>& a, hipStream_t s, long nwg) {
-    snprintf(g_last_kernel, sizeof(g_last_kernel), "nt_kernel<%s,%d,%d,%d,%d,%d,%d,%d>", Elem<T>::kName, WAVES_M, BN, KCH, MODE, NST, ROLE, ROLE == 1 ? a.bn_mode : 0);
+    // (",sub": the SUB instantiation -- a launch with a compact addend reads other bytes than its plain twin and is booked apart from it)
+    snprintf(g_last_kernel, sizeof(g_last_kernel), "nt_kernel<%s,%d,%d,%d,%d,%d,%d,%d%s>", Elem<T>::kName, WAVES_M, BN, KCH, MODE, NST, ROLE, ROLE == 1 ? a.bn_mode : 0,
+             (ROLE == 1 && a.add_sub) ? ",sub" : "");
     const dim3 grid((unsigned)nwg), block(128 * WAVES_M);
+    if (ROLE == 1 && a.add_sub) {   // compact addend (checked by launch_nt: dense, not with the T side product)
+        if constexpr (ROLE == 1 && MODE == MODE_DENSE) {
+            // the epilogues a conv1 data gradient of an entry block runs: none, mask from a_out (1), mask bits (4), mask bits and sum dz only
+            // (5).  With a BN mode the launch leaves partial sums behind and so never takes the 64-row tiles (launch_nt_mode).
+            switch (a.bn_mode) {
+                case 0: hipLaunchKernelGGL((nt_kernel<T, WAVES_M, BN, KCH, MODE, NST, ROLE, 0, true>), grid, block, 0, s, a); break;
+                case 1:
+                    if constexpr (WAVES_M == 2) { hipLaunchKernelGGL((nt_kernel<T, WAVES_M, BN, KCH, MODE, NST, ROLE, 1, true>), grid, block, 0, s, a); break; }
+                    else return rpe_set_error(RPE_ERR_SHAPE, "igemm_nt: a subsampled addend with a BN-backward mode is a 128-row launch");
+                case 4:
+                    if constexpr (WAVES_M == 2) { hipLaunchKernelGGL((nt_kernel<T, WAVES_M, BN, KCH, MODE, NST, ROLE, 4, true>), grid, block, 0, s, a); break; }
+                    else return rpe_set_error(RPE_ERR_SHAPE, "igemm_nt: a subsampled addend with a BN-backward mode is a 128-row launch");
+                case 5:
+                    if constexpr (sizeof(T) == 2 && WAVES_M == 2) { hipLaunchKernelGGL((nt_kernel<T, WAVES_M, BN, KCH, MODE, NST, ROLE, 5, true>), grid, block, 0, s, a); break; }
+                    else return rpe_set_error(RPE_ERR_SHAPE, "igemm_nt: BN-backward mode 5 is a dense 128-row launch of a 16-bit element type");
+                default: return rpe_set_error(RPE_ERR_SHAPE, "igemm_nt: a subsampled addend goes with no BN epilogue or with a ReLU mask from a_out or a_mask (modes 1, 4, 5)");
+            }
+        } else {
+            return rpe_set_error(RPE_ERR_SHAPE, "igemm_nt: a subsampled addend needs a dense data gradient");
+        }
+    } else
     if (ROLE == 1) {
         switch (a.bn_mode) {
             case 1: hipLaunchKernelGGL((nt_kernel<T, WAVES_M, BN, KCH, MODE, NST, ROLE, ROLE == 1 ? 1 : 0>), grid, block, 0, s, a); break;

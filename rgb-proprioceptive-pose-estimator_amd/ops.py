@@ -89,19 +89,32 @@ def conv2d_fwd_affine(x, w_krsc, stride, pad, bias, addend=None, relu=True, spli
     return out
 
 
-def conv2d_dgrad(dy, w_crsk, x_shape, stride, pad, addend=None):
-    """dy [B,Ho,Wo,Co], w_crsk [Ci,kh,kw,Co] -> dx [B,H,W,Ci] (+ addend)."""
+def conv2d_dgrad(dy, w_crsk, x_shape, stride, pad, addend=None, sub_addend=False):
+    """dy [B,Ho,Wo,Co], w_crsk [Ci,kh,kw,Co] -> dx [B,H,W,Ci] (+ addend).
+    sub_addend: `addend` is a compact shortcut gradient [B,H/2,W/2,Ci] (conv1x1s2_dgrad_compact), added at the even pixels."""
     _chk(dy, "dy"), _chk(w_crsk, "w")
     ci, k, co = w_crsk.shape[0], w_crsk.shape[1], w_crsk.shape[3]
     d = conv_desc(x_shape, co, k, stride, pad)
     dx = torch.empty(tuple(x_shape), dtype=dy.dtype, device=dy.device)
-    lib.rpe_conv2d_dgrad(ctypes.byref(d), dtype_code(dy), _p(dy), _p(w_crsk), _p(dx), _p(addend), _stream())
+    fn = lib.rpe_conv2d_dgrad_sub if sub_addend else lib.rpe_conv2d_dgrad
+    fn(ctypes.byref(d), dtype_code(dy), _p(dy), _p(w_crsk), _p(dx), _p(addend), _stream())
     return dx
 
 
-def conv2d_dgrad_bn(dy, w_crsk, x_shape, stride, pad, y, mean, invstd, a_out=None, scale=None, shift=None, addend=None, a_mask=None):
+def conv1x1s2_dgrad_compact(dy, w_crsk, x_shape):
+    """Data gradient of a 1x1 / stride-2 / pad-0 conv over even dims, on the pixels it reads alone: dy [B,H/2,W/2,Co], w_crsk [Ci,1,1,Co]
+    -> [B,H/2,W/2,Ci] = rows (b, 2h', 2w') of conv2d_dgrad's dx (every other row of it is zero)."""
+    _chk(dy, "dy"), _chk(w_crsk, "w")
+    ci, k, co = w_crsk.shape[0], w_crsk.shape[1], w_crsk.shape[3]
+    d = conv_desc(x_shape, co, k, 2, 0)
+    dx = torch.empty((x_shape[0], x_shape[1] // 2, x_shape[2] // 2, ci), dtype=dy.dtype, device=dy.device)
+    lib.rpe_conv1x1s2_dgrad_compact(ctypes.byref(d), dtype_code(dy), _p(dy), _p(w_crsk), _p(dx), _stream())
+    return dx
+
+
+def conv2d_dgrad_bn(dy, w_crsk, x_shape, stride, pad, y, mean, invstd, a_out=None, scale=None, shift=None, addend=None, a_mask=None, sub_addend=False):
     """Data gradient with the producing layer's ReLU mask and BN-backward partial sums fused into the epilogue.
-    Returns (dz [B,H,W,Ci], stats partials [tiles,2,Ci])."""
+    Returns (dz [B,H,W,Ci], stats partials [tiles,2,Ci]).  sub_addend: as conv2d_dgrad."""
     _chk(dy, "dy"), _chk(w_crsk, "w")
     if y is not None:   # (y = None with a_mask: the producing layer's raw output was never written -- only sum dz is emitted)
         _chk(y, "y")
@@ -110,7 +123,8 @@ def conv2d_dgrad_bn(dy, w_crsk, x_shape, stride, pad, y, mean, invstd, a_out=Non
     dz = torch.empty(tuple(x_shape), dtype=dy.dtype, device=dy.device)
     st = torch.empty((lib.rpe_conv2d_dgrad_stats_tiles(ctypes.byref(d), dtype_code(dy)), 2, ci), dtype=torch.float32, device=dy.device)
     ep = BnBwdEpilogue(*(None if t is None else t.data_ptr() for t in (y, a_out, mean, invstd, scale, shift, st, a_mask)))
-    lib.rpe_conv2d_dgrad_bn(ctypes.byref(d), dtype_code(dy), _p(dy), _p(w_crsk), _p(dz), _p(addend), ctypes.byref(ep), _stream())
+    fn = lib.rpe_conv2d_dgrad_bn_sub if sub_addend else lib.rpe_conv2d_dgrad_bn
+    fn(ctypes.byref(d), dtype_code(dy), _p(dy), _p(w_crsk), _p(dz), _p(addend), ctypes.byref(ep), _stream())
     return dz, st
 
 
@@ -238,20 +252,21 @@ def bn_bwd_fold_y_conv1x1(w_dgrad, gamma, invstd, mean, c1c2):
     return wk, bias
 
 
-def conv1x1_dgrad_kcat_y(dz, y, w_kcat, bias, ci, addend=None, bn=None):
+def conv1x1_dgrad_kcat_y(dz, y, w_kcat, bias, ci, addend=None, bn=None, sub_addend=False):
     """dz, y [B,H,W,Co] -> dx [B,H,W,Ci] = [dz | y] w_kcat^T + bias (+ addend).  bn: optional dict(y, mean, invstd, a_out / a_mask, scale,
-    shift) of the layer BEHIND dx (fused ReLU mask + BN-backward partial sums); then returns (dz_in, stats)."""
+    shift) of the layer BEHIND dx (fused ReLU mask + BN-backward partial sums); then returns (dz_in, stats).  sub_addend: as conv2d_dgrad."""
     _chk(dz, "dz"), _chk(y, "y")
     b, h, w, co = dz.shape
     d = conv_desc((b, h, w, ci), co, 1, 1, 0)
     dx = torch.empty((b, h, w, ci), dtype=dz.dtype, device=dz.device)
+    fn = lib.rpe_conv1x1_dgrad_kcat_y_sub if sub_addend else lib.rpe_conv1x1_dgrad_kcat_y
     if bn is None:
-        lib.rpe_conv1x1_dgrad_kcat_y(ctypes.byref(d), dtype_code(dz), _p(dz), _p(y), _p(w_kcat), _p(bias), _p(dx), _p(addend), None, _stream())
+        fn(ctypes.byref(d), dtype_code(dz), _p(dz), _p(y), _p(w_kcat), _p(bias), _p(dx), _p(addend), None, _stream())
         return dx
     st = torch.empty((lib.rpe_conv2d_dgrad_stats_tiles(ctypes.byref(d), dtype_code(dz)), 2, ci), dtype=torch.float32, device=dz.device)
     ep = BnBwdEpilogue(*(None if t is None else t.data_ptr() for t in (bn["y"], bn.get("a_out"), bn["mean"], bn["invstd"], bn.get("scale"), bn.get("shift"), st,
                                                                       bn.get("a_mask"))))
-    lib.rpe_conv1x1_dgrad_kcat_y(ctypes.byref(d), dtype_code(dz), _p(dz), _p(y), _p(w_kcat), _p(bias), _p(dx), _p(addend), ctypes.byref(ep), _stream())
+    fn(ctypes.byref(d), dtype_code(dz), _p(dz), _p(y), _p(w_kcat), _p(bias), _p(dx), _p(addend), ctypes.byref(ep), _stream())
     return dx, st
 
 
