@@ -500,6 +500,68 @@ int rpe_saliency_map(const float* scores, int M, const rpe_occlusion_desc* d, fl
 int rpe_saliency_overlay_u8(const unsigned char* frame, const float* map, const float* minmax, const unsigned char* table, int Hs, int Ws,
                             int alpha_q8, int fade, unsigned char* out, void* stream);
 
+/* ------------------------------------------------------------------ pose overlay */
+/* replaces: the second pass of the reference's rollout (util/learn_utils.py:401-403, 462-504: an indicator object moved to every estimated
+ * position inside the simulator, frames recorded) without the simulator: poses are projected through a camera matrix and drawn on the
+ * recorded uint8 frames.  Two launches; everything floating-point sits in the first, the second is integer only ("Pose
+ * overlay"; tests/_overlay_oracle.py restates both).
+ * Convention: [u w, v w, w] = P [x, y, z, 1]; u is the column and v the row of the frame AS STORED, pixel centres at integers.
+ * Coordinates are Q4 (1/16 pixel) int32.  RPE_OVERLAY_INVALID in BOTH components marks a point that draws nothing. */
+#define RPE_OVERLAY_INVALID (-2147483647 - 1)
+#define RPE_OVERLAY_NEAR 0.0009765625 /* 2^-10: a point with w <= this is behind (or in) the camera */
+#define RPE_OVERLAY_CLAMP_Q4 131072   /* 2^17: |coordinate| of a valid point */
+#define RPE_OVERLAY_AXIS_Q4 8192      /* 2^13: |tip - centre| per component of a valid axis (512 px) */
+#define RPE_OVERLAY_MAX_SETS 4
+#define RPE_OVERLAY_MAX_TRAIL 64
+#define RPE_OVERLAY_MAX_RADIUS_Q4 256
+#define RPE_OVERLAY_MAX_SIDE 4096
+/* poses: device, [F][G][7] fp32 (x, y, z, qx, qy, qz, qw), 1 <= G <= 4; cam: device, [C][3][4] fp64; cam_index: device, [F] int32 in
+ * [0, C) (an index outside invalidates the frame's points); pos_err, ori_err: device, [F] fp32, both or neither.
+ * points: device, [F][G][4][2] int32 = centre, tip of x, y, z axis, each (u, v) in Q4; bars: device, [F][2] int32.
+ * One thread per (frame, pose set).  Every operation is an fp64 + - * / or sqrt, none contracted, in this order:
+ *   h_r(X) = ((P[r][0] X0 + P[r][1] X1) + P[r][2] X2) + P[r][3] for r = 0, 1, 2;  (uw, vw, w) = h(X)
+ *   X is valid iff uw, vw and w are finite and w > RPE_OVERLAY_NEAR (a non-finite pose or matrix entry makes them non-finite)
+ *   u_q4 = clamp(floor(16 (uw / w) + 0.5), -2^17, 2^17), v_q4 alike
+ *   n = sqrt(((qx qx + qy qy) + qz qz) + qw qw); the tips are invalid unless 0 < n < inf; (a, b, c, d) = q / n
+ *   R e_0 = (1 - 2 (b b + c c), 2 (a b + c d), 2 (a c - b d));  R e_1 = (2 (a b - c d), 1 - 2 (a a + c c), 2 (b c + a d))
+ *   R e_2 = (2 (a c + b d), 2 (b c - a d), 1 - 2 (a a + b b));  tip_i = p + axis_len (R e_i), component by component
+ * A tip is invalid as well when the centre is, or when it lies more than RPE_OVERLAY_AXIS_Q4 from the centre in either component.
+ * bars[f] = (bar(pos_err[f], pos_full), bar(ori_err[f], ori_full)), bar(e, full) = clamp(floor(((double)e / full) width), 0, width),
+ * 0 for a NaN; (0, 0) without errors.  pos_full, ori_full > 0, 0 <= width <= 4096, axis_len finite. */
+int rpe_project_poses(const float* poses, const double* cam, const int* cam_index, long F, int G, int C, double axis_len, const float* pos_err,
+                      const float* ori_err, double pos_full, double ori_full, int width, int* points, int* bars, void* stream);
+/* how one pose set is drawn; _lib.OverlayStyle mirrors the layout (32 bytes) */
+typedef struct {
+    unsigned char rgb[3];        /* the disc's and the trail's colour */
+    unsigned char axis_rgb[9];   /* the colours of the x, y and z axis */
+    int alpha_q8;                /* opacity, [0, 256] */
+    int r_q4;                    /* disc radius, [0, 256] */
+    int hw_q4;                   /* half the axes' width, [0, 256] */
+    int trail;                   /* N: the centres of the N frames before are drawn too, [0, 64] */
+    int trail_r_q4;              /* their radius, [0, 256] */
+} rpe_overlay_style;
+/* frames: device, [n][Hs][Ws][3] uint8; out: device, the same shape, disjoint from it; points / bars: device, as rpe_project_poses
+ * writes them for F >= first + n frames -- frame i of `frames` is frame first + i of the list; styles: HOST, G of them.
+ * Integer arithmetic only.  A point is used when neither component is RPE_OVERLAY_INVALID and both lie within +-2^17; an axis when
+ * its centre and tip are and |tip - centre| <= 2^13 in both components.  Pixel (x, y) has four subsamples (16 x +- 4, 16 y +- 4); the
+ * coverage of a shape is the number of them inside it:
+ *   disc (c, r):      d = s - c;  d.d <= r r
+ *   capsule (c, tip, hw): e = tip - c, v = s - c, t = v.e, L = e.e;  t <= 0: v.v <= hw hw;  t >= L: (v - e).(v - e) <= hw hw;
+ *                     otherwise (v x e)^2 <= hw hw L;  only subsamples with lo - 8 <= s <= hi + 8 per component, lo / hi = min / max of
+ *                     (c, tip) -/+ hw, are looked at, so |v| <= 2^13 + 2^9 per component and |t|, |v x e| < 2^28, (v x e)^2 < 2^56, hw hw L <= 2^43: int64
+ * and a shape of colour k with coverage cov changes a byte to (px (1024 - w) + k w + 512) >> 10, w = cov * alpha (w = 0: unchanged).
+ * Order: first, per set g = 0 .. G-1, the trail -- with t = (first + i) mod frames_per_episode, the union of the discs of radius
+ * trail_r_q4 at the usable centres of set g in frames first + i - k, 1 <= k <= min(N, t), as ONE shape with alpha = alpha_q8 >> 1;
+ * then, per set, the axes x, y, z (alpha_q8, their colours) and the disc (alpha_q8, rgb).
+ * bar_px > 0: output rows Hs - 2 bar_px .. Hs - bar_px - 1 (band 0) and Hs - bar_px .. Hs - 1 (band 1) show, after the shapes, the colour
+ * bar_rgb[3 band ..] where x < bars[first + i][band] and the byte >> 1 elsewhere; 2 bar_px <= Hs; bar_rgb: HOST, 6 bytes.
+ * flip: stored row y is written to output row Hs - 1 - y (the bars are at the bottom of the OUTPUT).  Drawing is in stored coordinates.
+ * A frame nothing is drawn on comes out byte-identical up to the flip.  16-byte loads and stores when Hs Ws 3 (with flip: Ws 3) and
+ * both pointers are multiples of 16, 4-byte when multiples of 4, single bytes otherwise.  One launch.
+ * Refused: n < 1, first < 0, Hs or Ws outside [1, 4096], G outside [1, 4], frames_per_episode < 1, a style outside its ranges. */
+int rpe_draw_poses_u8(const unsigned char* frames, unsigned char* out, long n, int Hs, int Ws, const int* points, const int* bars, long first, int G,
+                      const rpe_overlay_style* styles, int frames_per_episode, int bar_px, const unsigned char* bar_rgb, int flip, void* stream);
+
 /* replaces: nn.Linear (+ F.relu) of the proprio-fusion MLP (models/naive.py:343-345), the
  * ResNet fc (util/model_utils.py:141), the LSTM input/recurrent GEMMs and the fc heads
  * (models/time_sensitive.py:420-423,510).  y[M][N] = x[M][K] w[N][K]^T (+bias) (+addend) (relu).

@@ -59,6 +59,15 @@ class OcclusionDesc(Structure):
     _fields_ = [(n, c_int) for n in ("Hs", "Ws", "ph", "pw", "sy", "sx")] + [("fill_rgb", ctypes.c_ubyte * 3)]
 
 
+class OverlayStyle(Structure):
+    """rpe_overlay_style"""
+    _fields_ = [("rgb", ctypes.c_ubyte * 3), ("axis_rgb", ctypes.c_ubyte * 9)] + [(n, c_int) for n in ("alpha_q8", "r_q4", "hw_q4", "trail", "trail_r_q4")]
+
+
+# RPE_OVERLAY_*: the draw list's sentinel and clamps (include/rpe_hip.h)
+OVERLAY_INVALID, OVERLAY_NEAR, OVERLAY_CLAMP_Q4, OVERLAY_AXIS_Q4 = -2 ** 31, 2.0 ** -10, 2 ** 17, 2 ** 13
+OVERLAY_MAX_SETS, OVERLAY_MAX_TRAIL, OVERLAY_MAX_RADIUS_Q4, OVERLAY_MAX_SIDE = 4, 64, 256, 4096
+
 P, I, L, F, D = c_void_p, c_int, c_long, c_float, c_double
 PD = POINTER(ConvDesc)
 
@@ -219,6 +228,8 @@ _SPEC = {
     "rpe_pose_displacement": (I, [P, P, L, P, P, P]),
     "rpe_saliency_map": (I, [P, I, POINTER(OcclusionDesc), P, P, P]),
     "rpe_saliency_overlay_u8": (I, [P, P, P, P, I, I, I, I, P, P]),
+    "rpe_project_poses": (I, [P, P, P, L, I, I, D, P, P, D, D, I, P, P, P]),
+    "rpe_draw_poses_u8": (I, [P, P, L, I, I, P, P, L, I, POINTER(OverlayStyle), I, I, POINTER(ctypes.c_ubyte), I, P]),
 }
 # entry points whose int return value is data, not a status
 _NOT_STATUS = {"rpe_abi_version", "rpe_conv2d_wgrad_halo_min_width", "rpe_grad_sumsq_rows", "rpe_param_stats_rows"}

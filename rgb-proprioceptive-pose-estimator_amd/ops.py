@@ -986,6 +986,135 @@ def saliency_overlay_u8(frame, smap, minmax, table, alpha_q8, fade=False):
     return out
 
 
+# the flat list form `torch.ops.rpe.draw_poses_u8` takes: these 17 integers per pose set
+OVERLAY_STYLE_FIELDS = ("r", "g", "b", "x_r", "x_g", "x_b", "y_r", "y_g", "y_b", "z_r", "z_g", "z_b", "alpha_q8", "r_q4", "hw_q4", "trail", "trail_r_q4")
+OVERLAY_AXIS_COLOURS = ((230, 40, 40), (40, 200, 40), (60, 90, 255))
+
+
+def _colour(name, c):
+    try:
+        vals = tuple(int(v) for v in c)
+    except TypeError:
+        vals = ()
+    if len(vals) != 3 or not all(0 <= v <= 255 for v in vals):
+        raise ValueError("%s: a colour is three bytes; got %r" % (name, c))
+    return vals
+
+
+def overlay_style(colour=(255, 255, 255), alpha_q8=256, r_q4=64, hw_q4=24, axis_colours=OVERLAY_AXIS_COLOURS, trail=0, trail_r_q4=32):
+    """rpe_overlay_style, how one pose set is drawn: the disc's and the trail's colour, opacity alpha_q8 in [0, 256], disc radius r_q4,
+    half the axes' width hw_q4 and the trail's radius trail_r_q4 in sixteenths of a pixel (each at most 256), the three axes' colours
+    and the trail length in frames (at most 64).  ValueError for anything rpe_draw_poses_u8 would refuse."""
+    from ._lib import OVERLAY_MAX_RADIUS_Q4, OVERLAY_MAX_TRAIL, OverlayStyle
+    s = OverlayStyle()
+    for i, v in enumerate(_colour("overlay_style", colour)):
+        s.rgb[i] = v
+    axes = tuple(axis_colours)
+    if len(axes) != 3:
+        raise ValueError("overlay_style: axis_colours are three colours; got %r" % (axis_colours,))
+    for k, c in enumerate(axes):
+        for i, v in enumerate(_colour("overlay_style", c)):
+            s.axis_rgb[3 * k + i] = v
+    if not 0 <= int(alpha_q8) <= 256:
+        raise ValueError("overlay_style: alpha_q8 lies in [0, 256]; got %r" % (alpha_q8,))
+    for name, v in (("r_q4", r_q4), ("hw_q4", hw_q4), ("trail_r_q4", trail_r_q4)):
+        if not 0 <= int(v) <= OVERLAY_MAX_RADIUS_Q4:
+            raise ValueError("overlay_style: %s lies in [0, %d] (sixteenths of a pixel); got %r" % (name, OVERLAY_MAX_RADIUS_Q4, v))
+    if not 0 <= int(trail) <= OVERLAY_MAX_TRAIL:
+        raise ValueError("overlay_style: the trail length lies in [0, %d]; got %r" % (OVERLAY_MAX_TRAIL, trail))
+    s.alpha_q8, s.r_q4, s.hw_q4, s.trail, s.trail_r_q4 = int(alpha_q8), int(r_q4), int(hw_q4), int(trail), int(trail_r_q4)
+    return s
+
+
+def overlay_style_from_list(vals):
+    """the 17 integers of OVERLAY_STYLE_FIELDS -> rpe_overlay_style"""
+    if len(vals) != len(OVERLAY_STYLE_FIELDS):
+        raise ValueError("a pose set's style has %d integers (%s)" % (len(OVERLAY_STYLE_FIELDS), ", ".join(OVERLAY_STYLE_FIELDS)))
+    v = [int(x) for x in vals]
+    return overlay_style(v[0:3], v[12], v[13], v[14], (v[3:6], v[6:9], v[9:12]), v[15], v[16])
+
+
+def overlay_style_to_list(s):
+    return list(s.rgb) + list(s.axis_rgb) + [s.alpha_q8, s.r_q4, s.hw_q4, s.trail, s.trail_r_q4]
+
+
+def project_poses(poses, cam, cam_index, axis_len=0.05, pos_err=None, ori_err=None, pos_full=0.1, ori_full=0.5, width=0):
+    """poses fp32 (F, G, 7) with G <= 4, cam fp64 (C, 3, 4), cam_index int32 (F,), all contiguous on one device -> (points int32
+    (F, G, 4, 2), bars int32 (F, 2)): per pose the centre and the tips of the three axes of length `axis_len` in sixteenths of a pixel
+    ([u w, v w, w] = P [x, y, z, 1], fp64), _lib.OVERLAY_INVALID where there is nothing to draw; with pos_err / ori_err fp32 (F,) the
+    lengths of the two error bars of a frame `width` pixels wide, full at pos_full / ori_full (rpe_project_poses)."""
+    from ._lib import OVERLAY_MAX_SETS, OVERLAY_MAX_SIDE
+    if poses.dtype != torch.float32 or poses.dim() != 3 or poses.shape[2] != 7 or poses.numel() == 0 or poses.shape[1] > OVERLAY_MAX_SETS:
+        raise ValueError("project_poses: poses must be fp32 (F, G, 7) with 1 <= G <= %d; got %s %r" % (OVERLAY_MAX_SETS, poses.dtype, tuple(poses.shape)))
+    f, g = poses.shape[:2]
+    dev = poses.device
+    if cam.dtype != torch.float64 or cam.dim() != 3 or tuple(cam.shape[1:]) != (3, 4) or cam.shape[0] < 1 or cam.device != dev:
+        raise ValueError("project_poses: cam must be fp64 (C, 3, 4) on the poses' device; got %s %r" % (cam.dtype, tuple(cam.shape)))
+    if cam_index.dtype != torch.int32 or tuple(cam_index.shape) != (f,) or cam_index.device != dev:
+        raise ValueError("project_poses: cam_index must be int32 (%d,) on the poses' device" % f)
+    if (pos_err is None) != (ori_err is None):
+        raise ValueError("project_poses: pos_err and ori_err come together")
+    for t, name in ((pos_err, "pos_err"), (ori_err, "ori_err")):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (f,) or t.device != dev):
+            raise ValueError("project_poses: %s must be fp32 (%d,) on the poses' device" % (name, f))
+    axis_len, pos_full, ori_full, width = float(axis_len), float(pos_full), float(ori_full), int(width)
+    if not (math.isfinite(axis_len) and math.isfinite(pos_full) and math.isfinite(ori_full) and pos_full > 0 and ori_full > 0):
+        raise ValueError("project_poses: axis_len must be finite, pos_full and ori_full finite and positive; got %r, %r, %r" % (axis_len, pos_full, ori_full))
+    if not 0 <= width <= OVERLAY_MAX_SIDE:
+        raise ValueError("project_poses: the width lies in [0, %d]; got %r" % (OVERLAY_MAX_SIDE, width))
+    points = torch.empty((f, g, 4, 2), dtype=torch.int32, device=dev)
+    bars = torch.empty((f, 2), dtype=torch.int32, device=dev)
+    lib.rpe_project_poses(_p(_chk(poses, "poses")), _p(_chk(cam, "cam")), _p(_chk(cam_index, "cam_index")), f, g, cam.shape[0], axis_len,
+                          _p(None if pos_err is None else _chk(pos_err, "pos_err")), _p(None if ori_err is None else _chk(ori_err, "ori_err")), pos_full,
+                          ori_full, width, _p(points), _p(bars), _stream())
+    return points, bars
+
+
+OVERLAY_BAR_COLOURS = ((255, 255, 255), (255, 200, 0))
+
+
+def draw_poses_u8(frames, points, bars, styles, *, frames_per_episode=1, first=0, bar_px=0, bar_colours=OVERLAY_BAR_COLOURS, flip=False, out=None):
+    """frames uint8 (n, Hs, Ws, 3), points int32 (F, G, 4, 2) and bars int32 (F, 2) as `project_poses` writes them with F >= first + n,
+    all contiguous on one device; styles: G `overlay_style`s -> uint8 (n, Hs, Ws, 3), frame i annotated with entry first + i of the
+    list: per pose set the trail of the earlier centres of the same episode (`frames_per_episode` entries each), the three axes and the
+    disc; with bar_px > 0 two error bars of that height at the bottom of the output, in `bar_colours`; with `flip` the rows are
+    written bottom up.  Integer arithmetic only (rpe_draw_poses_u8).  out: destination, contiguous, not overlapping the frames."""
+    from ._lib import OVERLAY_MAX_SETS, OVERLAY_MAX_SIDE, OverlayStyle
+    if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3 or frames.numel() == 0:
+        raise ValueError("draw_poses_u8: frames must be uint8 (n, Hs, Ws, 3); got %s %r" % (frames.dtype, tuple(frames.shape)))
+    n, hs, ws = frames.shape[:3]
+    dev = frames.device
+    if hs > OVERLAY_MAX_SIDE or ws > OVERLAY_MAX_SIDE:
+        raise ValueError("draw_poses_u8: frames are at most %d pixels a side; got %d x %d" % (OVERLAY_MAX_SIDE, hs, ws))
+    styles = list(styles)
+    g = len(styles)
+    if not 1 <= g <= OVERLAY_MAX_SETS or not all(isinstance(s, OverlayStyle) for s in styles):
+        raise ValueError("draw_poses_u8: styles are 1..%d overlay_style(...) values, one per pose set" % OVERLAY_MAX_SETS)
+    first, fpe, bar_px = int(first), int(frames_per_episode), int(bar_px)
+    if points.dtype != torch.int32 or points.dim() != 4 or tuple(points.shape[1:]) != (g, 4, 2) or points.device != dev:
+        raise ValueError("draw_poses_u8: points must be int32 (F, %d, 4, 2) on the frames' device; got %s %r" % (g, points.dtype, tuple(points.shape)))
+    if bars.dtype != torch.int32 or tuple(bars.shape) != (points.shape[0], 2) or bars.device != dev:
+        raise ValueError("draw_poses_u8: bars must be int32 (%d, 2) on the frames' device" % points.shape[0])
+    if first < 0 or first + n > points.shape[0]:
+        raise ValueError("draw_poses_u8: frames %d .. %d are not in a list of %d" % (first, first + n - 1, points.shape[0]))
+    if fpe < 1:
+        raise ValueError("draw_poses_u8: frames_per_episode must be at least 1; got %r" % (frames_per_episode,))
+    if bar_px < 0 or 2 * bar_px > hs:
+        raise ValueError("draw_poses_u8: two bars of %d rows do not fit %d rows" % (bar_px, hs))
+    cols = tuple(bar_colours)
+    if len(cols) != 2:
+        raise ValueError("draw_poses_u8: bar_colours are two colours; got %r" % (bar_colours,))
+    rgb6 = (ctypes.c_ubyte * 6)(*(_colour("draw_poses_u8", cols[0]) + _colour("draw_poses_u8", cols[1])))
+    if out is None:
+        out = torch.empty_like(frames)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != tuple(frames.shape) or out.device != dev:
+        raise ValueError("draw_poses_u8: out must be uint8 %r on the frames' device" % (tuple(frames.shape),))
+    arr = (OverlayStyle * g)(*styles)
+    lib.rpe_draw_poses_u8(_p(_chk(frames, "frames")), _p(_chk(out, "out")), n, hs, ws, _p(_chk(points, "points")), _p(_chk(bars, "bars")), first, g, arr,
+                          fpe, bar_px, rgb6, int(bool(flip)), _stream())
+    return out
+
+
 MEASURE_MAX_SCALES = 8
 # the flat list form `torch.ops.rpe.measurement_noise` takes: these five numbers, then the 1..8 variances (the seed travels as two
 # 32-bit words because a double does not hold 64 bits)

@@ -22,6 +22,8 @@ ResNet; models/losses.py:114-128 is the loss; util/learn_utils.py:152-184 the st
     rpe::measurement_noise                          x0 + sqrt(scale) * randn_like(x0) with the quaternion renormalised (util/data_utils.py:162-167), drawn on the device
     rpe::occlude_grid_u8 / pose_displacement /      (no counterpart: occlusion sensitivity) a frame with one rectangle of a grid covered per row; how far
     rpe::saliency_map / saliency_overlay_u8         each prediction moved; the scores spread over the pixels; the map drawn over the frame
+    rpe::project_poses / draw_poses_u8              the recorded video of rollout() (util/learn_utils.py:401-403, 462-504) without the simulator: poses through a camera
+                                                    matrix to an integer draw list; the list drawn on the recorded uint8 frames
 
 Importing this module needs torch only; the HIP library is loaded on the first call (ops.py), so the schemas can be inspected on a
 machine without a GPU (tests/test_host_cpu.py).
@@ -34,7 +36,7 @@ __all__ = ["NAMES"]
 
 _NS = "rpe"
 NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step", "augment_frames_u8", "sample_windows", "gather_rows",
-         "measurement_noise", "occlude_grid_u8", "pose_displacement", "saliency_map", "saliency_overlay_u8", "param_stats")
+         "measurement_noise", "occlude_grid_u8", "pose_displacement", "saliency_map", "saliency_overlay_u8", "param_stats", "project_poses", "draw_poses_u8")
 
 
 def _ops():
@@ -315,3 +317,36 @@ def saliency_overlay_u8(frame: torch.Tensor, smap: torch.Tensor, minmax: torch.T
 @saliency_overlay_u8.register_fake
 def _(frame, smap, minmax, table, alpha_q8, fade):
     return torch.empty_like(frame)
+
+
+# ---- pose overlay --------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op(_NS + "::project_poses", mutates_args=(), device_types="cuda")
+def project_poses(poses: torch.Tensor, cam: torch.Tensor, cam_index: torch.Tensor, axis_len: float, pos_err: Optional[torch.Tensor],
+                  ori_err: Optional[torch.Tensor], pos_full: float, ori_full: float, width: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """poses fp32 (F, G, 7), cam fp64 (C, 3, 4), cam_index int32 (F,) -> (points int32 (F, G, 4, 2) in sixteenths of a pixel, bars int32 (F, 2))"""
+    points, bars = _ops().project_poses(poses, cam, cam_index, axis_len, pos_err, ori_err, pos_full, ori_full, width)
+    return points, bars
+
+
+@project_poses.register_fake
+def _(poses, cam, cam_index, axis_len, pos_err, ori_err, pos_full, ori_full, width):
+    return poses.new_empty((poses.shape[0], poses.shape[1], 4, 2), dtype=torch.int32), poses.new_empty((poses.shape[0], 2), dtype=torch.int32)
+
+
+@torch.library.custom_op(_NS + "::draw_poses_u8", mutates_args=(), device_types="cuda")
+def draw_poses_u8(frames: torch.Tensor, points: torch.Tensor, bars: torch.Tensor, styles: List[int], frames_per_episode: int, first: int, bar_px: int,
+                  bar_colours: List[int], flip: bool) -> torch.Tensor:
+    """frames uint8 (n, Hs, Ws, 3) annotated with entries first .. first + n - 1 of the draw list; styles: per pose set the integers of
+    rpe_overlay_style in the order of ops.OVERLAY_STYLE_FIELDS, one set after the other; bar_colours: six bytes"""
+    ops = _ops()
+    k = len(ops.OVERLAY_STYLE_FIELDS)
+    if not styles or len(styles) % k or len(bar_colours) != 6:
+        raise ValueError("draw_poses_u8: styles has %d integers per pose set (%s), bar_colours six" % (k, ", ".join(ops.OVERLAY_STYLE_FIELDS)))
+    sets = [ops.overlay_style_from_list(styles[i:i + k]) for i in range(0, len(styles), k)]
+    return ops.draw_poses_u8(frames, points, bars, sets, frames_per_episode=frames_per_episode, first=first, bar_px=bar_px,
+                             bar_colours=(bar_colours[:3], bar_colours[3:]), flip=flip)
+
+
+@draw_poses_u8.register_fake
+def _(frames, points, bars, styles, frames_per_episode, first, bar_px, bar_colours, flip):
+    return torch.empty_like(frames)

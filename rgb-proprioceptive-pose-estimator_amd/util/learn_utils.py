@@ -11,7 +11,8 @@ Same signature, phases, criterion dict, statistics and checkpoint naming as trai
     SUM-all-reduced (RCCL) between backward and the optimizer step.
 rollout() of the reference needs the simulator and is out of scope; its model side -- every episode
 walked step by step, per-step position / orientation errors, their per-episode and overall statistics (util/learn_utils.py:
-446-538) -- is `evaluate_episodes`: all episodes advance together as lanes of one batch and the errors stay on the device.
+446-538) -- is `evaluate_episodes`: all episodes advance together as lanes of one batch and the errors stay on the device; its
+recorded video (util/learn_utils.py:401-403, 462-504) is `render_episodes` / `write_video`: the poses drawn on the recorded frames.
 """
 import contextlib
 import copy
@@ -434,6 +435,146 @@ def evaluate_episodes(model, dataset, num_episodes, params, *, max_frames=256, n
     if scales is None:
         outputs, poses, pos, ori, meas = outputs[0], poses[0], pos[0], ori[0], meas[0]
     return EpisodeEvaluation(outputs, poses, pos, ori, stats, scales, truth=truth, measurements=meas)
+
+
+# ---- rollout video: the estimate and the truth drawn on the recorded frames ------------------------------------------------------
+# The reference records its videos inside the simulator (util/learn_utils.py:401-403, 462-504: an indicator object is moved to each
+# estimated position and the camera is rendered again).  Here the poses of an EpisodeEvaluation are projected through the camera's
+# matrix and drawn on the recorded uint8 frames, both on the device (rpe_project_poses, rpe_draw_poses_u8; DESIGN.md "Pose overlay").
+OVERLAY_SETS = ("truth", "estimate", "measurement")
+OVERLAY_COLOURS = {"truth": (40, 220, 40), "estimate": (255, 60, 200), "measurement": (90, 160, 255)}
+OVERLAY_ORI_BAR_COLOUR = (255, 150, 0)     # the orientation-error bar; the position-error bar has the estimate's colour
+
+
+def flip_camera_rows(P, Hs):
+    """A camera matrix (..., 3 or 4, 4) given for the UPRIGHT picture of Hs rows -> the matrix for the picture as stored upside down
+    (robosuite's frames; the reference writes img[::-1]): the row coordinate v becomes Hs - 1 - v, that is row 1 of the matrix
+    becomes (Hs - 1) row 2 - row 1.  float64 numpy; the input is not changed."""
+    P = np.array(P, dtype=np.float64)
+    if P.ndim < 2 or P.shape[-1] != 4 or P.shape[-2] not in (3, 4):
+        raise ValueError("a camera matrix is (3, 4) or (4, 4); got {}".format(P.shape))
+    P[..., 1, :] = (int(Hs) - 1) * P[..., 2, :] - P[..., 1, :]
+    return P
+
+
+def _camera_matrices(camera, num_episodes, device):
+    """camera (3|4, 4) or (E, 3|4, 4) -> (fp64 (C, 3, 4) on the device, whether there is one per episode)"""
+    cam = camera if isinstance(camera, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(camera, dtype=np.float64)))
+    if cam.dim() not in (2, 3) or cam.shape[-1] != 4 or cam.shape[-2] not in (3, 4) or not (cam.is_floating_point()):
+        raise ValueError("camera must be a (3, 4) or (4, 4) matrix, or one per episode (E, ., 4); got {} {}".format(cam.dtype, tuple(cam.shape)))
+    if cam.dim() == 3 and cam.shape[0] != num_episodes:
+        raise ValueError("camera holds {} matrices for {} episodes".format(cam.shape[0], num_episodes))
+    per_episode = cam.dim() == 3
+    cam = cam.reshape(-1, cam.shape[-2], 4)[:, :3].to(device=device, dtype=torch.float64).contiguous()
+    return cam, per_episode
+
+
+def render_episodes(evaluation, frames, camera, *, draw=("truth", "estimate"), axis_len=0.05, radius=4.0, axis_width=1.5, trail=8, bars=True,
+                    pos_full=0.1, ori_full=0.5, alpha=1.0, flip=True, colours=None, scale=0, chunk=256, out=None):
+    """The rollout video: the poses of `evaluation` (an EpisodeEvaluation of E episodes of T steps) drawn on the recorded frames
+    -> uint8 (E, T, Hs, Ws, 3) on the device.
+
+    frames: the RAW uint8 frames (E, T, Hs, Ws, 3) the episodes were scored on, host or device; `chunk` frames at a time are moved and
+    drawn, so a host array need not fit the device twice.  camera: the 3 x 4 matrix P with [u w, v w, w] = P [x, y, z, 1], u the column
+    and v the row of the frame AS STORED (`flip_camera_rows` converts a matrix of the upright picture), as (3, 4) or (4, 4) -- the
+    first three rows are used -- or one per episode (E, ., 4); numpy or tensor, used in fp64.
+    draw: which of "truth", "estimate" (evaluation.poses), "measurement" to draw, in drawing order.  Each is a disc of `radius` pixels
+    at the projected position, three axes of `axis_len` metres and `axis_width` pixels showing the orientation, and the positions of
+    the `trail` steps before in the same episode, fainter.  bars: two bars along the bottom edge show the step's position error (full
+    width at `pos_full` metres) and orientation error (`ori_full` radians).  alpha: opacity in [0, 1].  flip: write the rows bottom
+    up, so that frames stored upside down come out upright.  colours: {set name: (r, g, b)} replacing OVERLAY_COLOURS.  scale: which
+    noise scale of a sweep.  out: destination, uint8 (E, T, Hs, Ws, 3) on the device, not overlapping `frames`.
+    One rpe_project_poses launch for all steps, then one rpe_draw_poses_u8 launch per chunk, on the current stream; nothing is
+    synchronised and nothing of the evaluation is changed.  Device only (no CPU fallback)."""
+    from .. import ops
+    sets = tuple(draw)
+    if not sets or len(sets) != len(set(sets)) or any(s not in OVERLAY_SETS for s in sets):
+        raise ValueError("draw lists one or more of {}, each once; got {!r}".format(", ".join(OVERLAY_SETS), draw))
+    swept = evaluation.noise_scales is not None
+    k = int(scale)
+    if not 0 <= k < (len(evaluation.noise_scales) if swept else 1):
+        raise ValueError("scale {!r}: the evaluation holds {} noise scale(s)".format(scale, len(evaluation.noise_scales) if swept else 1))
+    pick = (lambda t: t[k]) if swept else (lambda t: t)
+    source = {"truth": evaluation.truth, "estimate": pick(evaluation.poses),
+              "measurement": None if evaluation.measurements is None else pick(evaluation.measurements)}
+    for s in sets:
+        if source[s] is None:
+            raise ValueError("the evaluation holds no {} poses".format(s))
+    dev = evaluation.poses.device
+    E, T = source[sets[0]].shape[:2]
+    if isinstance(frames, np.ndarray):
+        frames = torch.from_numpy(frames)
+    if not isinstance(frames, torch.Tensor) or frames.dtype != torch.uint8 or frames.dim() != 5 or frames.shape[-1] != 3:
+        raise ValueError("render_episodes draws on RAW uint8 frames (E, T, Hs, Ws, 3), not on resized or normalised images; got {} {}".format(
+            getattr(frames, "dtype", type(frames)), tuple(getattr(frames, "shape", ()))))
+    if tuple(frames.shape[:2]) != (E, T):
+        raise ValueError("frames of {} episodes x {} steps for an evaluation of {} x {}".format(frames.shape[0], frames.shape[1], E, T))
+    if frames.is_cuda and frames.device != dev:
+        raise ValueError("frames on {} and the evaluation on {}".format(frames.device, dev))
+    Hs, Ws = frames.shape[2:4]
+    if not 0.0 <= float(alpha) <= 1.0:
+        raise ValueError("alpha lies in [0, 1]; got {!r}".format(alpha))
+    if not (float(radius) >= 0 and float(axis_width) >= 0):
+        raise ValueError("radius and axis_width are not negative; got {!r}, {!r}".format(radius, axis_width))
+    if int(chunk) < 1:
+        raise ValueError("chunk must be at least 1; got {!r}".format(chunk))
+    colour = dict(OVERLAY_COLOURS)
+    for name, c in (colours or {}).items():
+        if name not in OVERLAY_SETS:
+            raise ValueError("colours: {!r} is none of {}".format(name, ", ".join(OVERLAY_SETS)))
+        colour[name] = c
+    r_q4 = int(round(float(radius) * 16))
+    styles = [ops.overlay_style(colour[s], int(round(float(alpha) * 256)), r_q4, int(round(float(axis_width) * 8)), ops.OVERLAY_AXIS_COLOURS, int(trail),
+                                r_q4 // 2) for s in sets]
+    cam, per_episode = _camera_matrices(camera, E, None)
+    if dev.type != "cuda":
+        raise RuntimeError("render_episodes(): the overlay runs on the MI355X HIP path only; there is no CPU fallback")
+    cam = cam.to(dev)
+    n = E * T
+    cam_index = (torch.arange(n, dtype=torch.int32, device=dev) // T) if per_episode else torch.zeros(n, dtype=torch.int32, device=dev)
+    poses = torch.stack([source[s].reshape(n, 7) for s in sets], dim=1).to(torch.float32).contiguous()
+    bar_px = max(1, Hs // 32) if bars and Hs >= 2 else 0
+    errs = (pick(evaluation.pos_err).reshape(n).contiguous(), pick(evaluation.ori_err).reshape(n).contiguous()) if bar_px else (None, None)
+    points, bar_len = ops.project_poses(poses, cam, cam_index, axis_len, errs[0], errs[1], pos_full, ori_full, Ws if bar_px else 0)
+    shape = (E, T, Hs, Ws, 3)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.uint8, device=dev)
+    elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != dev or not out.is_contiguous():
+        raise ValueError("out must be a contiguous uint8 {} tensor on {}".format(shape, dev))
+    if frames.is_cuda:
+        lo, hi = frames.data_ptr(), frames.data_ptr() + frames.numel()
+        if out.data_ptr() < hi and lo < out.data_ptr() + out.numel():
+            raise ValueError("out overlaps frames: the frames are read while the output is written")
+    flat, out_flat = frames.reshape(n, Hs, Ws, 3), out.view(n, Hs, Ws, 3)
+    bar_colours = (colour["estimate"] if "estimate" in sets else colour[sets[0]], OVERLAY_ORI_BAR_COLOUR)
+    for i in range(0, n, int(chunk)):
+        src = flat[i:i + int(chunk)]
+        src = (src if src.is_cuda else src.to(dev, non_blocking=True)).contiguous()
+        ops.draw_poses_u8(src, points, bar_len, styles, frames_per_episode=T, first=i, bar_px=bar_px, bar_colours=bar_colours, flip=flip,
+                          out=out_flat[i:i + src.shape[0]])
+    return out
+
+
+def write_video(frames, path, fps=10):
+    """Write uint8 frames (..., Hs, Ws, 3) -- all leading dimensions are the frames in order, as render_episodes returns them -- to
+    `path`: `.npy` holds the raw (N, Hs, Ws, 3) array, `.gif` an animation at `fps` frames a second (Pillow)."""
+    ext = os.path.splitext(str(path))[1].lower()
+    if ext not in (".npy", ".gif"):
+        raise ValueError("write_video writes .npy (the raw array) or .gif; got {!r}".format(path))
+    if not float(fps) > 0:
+        raise ValueError("fps must be positive; got {!r}".format(fps))
+    arr = frames.detach().cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
+    if arr.dtype != np.uint8 or arr.ndim < 4 or arr.shape[-1] != 3 or arr.size == 0:
+        raise ValueError("frames must be uint8 (..., Hs, Ws, 3); got {} {}".format(arr.dtype, arr.shape))
+    arr = np.ascontiguousarray(arr.reshape((-1,) + arr.shape[-3:]))
+    if ext == ".npy":
+        with open(path, "wb") as f:
+            np.save(f, arr)
+        return path
+    from PIL import Image
+    pics = [Image.fromarray(a, "RGB") for a in arr]
+    pics[0].save(path, format="GIF", save_all=True, append_images=pics[1:], duration=max(1, int(round(1000.0 / float(fps)))), loop=0)
+    return path
 
 
 def _telemetry_host(optimizer):
