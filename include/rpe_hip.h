@@ -326,6 +326,45 @@ typedef struct {
  * picks: device, 1 + N ints, receives [0] = the step used, [1 + n] = the scale index lane n drew.  Two launches. */
 int rpe_measurement_noise(const float* x0, float* out, const rpe_measure_desc* d, unsigned* state, int* picks, void* stream);
 
+/* Depth-sensor augmentation of raw depth frames (replaces nothing: the reference's depth transform is deterministic), fp32
+ * [B][Hs][Ws] in, fp32 out, in front of rpe_stage_depth_f32_resized ("Depth augmentation").  Per pixel d, in this order:
+ *   1 noise (any n_i != 0): sd = (n0 + n1 d) + (n2 d) d, v = d + sd (double)T with the integer T = 2 (h0 + .. + h5) - 6 * 65535 over
+ *     the six 16-bit halves of the pixel's words r0, r1, r2 (low half first); Var T = 2 (2^32 - 1), so n_i = sigma_i / sqrt(2 (2^32 - 1))
+ *   2 quantisation (q > 0): v = rint(v inv_q) q, round half even
+ *   3 clamp: v = v < lo ? lo : v, then v = v > hi ? hi : v (lo = -inf and hi = +inf: off)
+ *   4 dropout: hole_value iff the pixel's word r3 < drop_thresh
+ *   5 holes: hole_value inside any of the first `count` of the stream's four rectangles
+ *   6 shared occluder (rgb_params given): occluder_value inside the rectangle of rpe_augment_frames_u8's table where the stream erases
+ * Later stages win.  1-3 are fp64 with one rounding to fp32 at the store, every product and sum rounded on its own (no fused
+ * multiply-add).  The input's bit pattern is copied where 1-3 are all off and for a non-finite input; a neutral descriptor is the
+ * identity.  Philox4x32-10 keyed by `seed`, bounded draws (r n) >> 32, counters
+ *   (g, 0, step, 0x44455048): count = hole_lo + draw(r0, hole_hi - hole_lo + 1) of stream g
+ *   (g, j, step, 0x44455052): rectangle j < 4: h = hh_lo + draw(r0, .), w = hw_lo + draw(r1, .), top = draw(r2, Hs - h + 1),
+ *                             left = draw(r3, Ws - w + 1); all four are drawn and tabled
+ *   (y Ws + x, b, step, 0x44455058): r0..r2 the noise, r3 the dropout of pixel (y, x) of frame b -- always per frame; run only when
+ *                             noise or dropout is on */
+typedef struct {
+    unsigned long long seed;          /* Philox key = (low word, high word) */
+    double n0, n1, n2;                /* noise coefficients, finite and >= 0; all 0 = off */
+    double q, inv_q;                  /* quantisation step and 1 / q, both computed on the host in double; q = 0: off */
+    double lo, hi;                    /* clamp range, lo <= hi */
+    unsigned drop_thresh;             /* probability * 2^32, capped at 2^32 - 1; 0 = off */
+    int hole_lo, hole_hi;             /* holes per stream, 0 <= lo <= hi <= 4 */
+    int hh_lo, hh_hi, hw_lo, hw_hi;   /* hole height / width bounds in pixels, 1 <= lo <= hi <= Hs / Ws (checked when hole_hi > 0) */
+    float hole_value, occluder_value; /* what a dropped / hole pixel and an occluded pixel become */
+    int group;                        /* 0: frame b draws its holes from stream b; N > 0: from stream b % N */
+} rpe_depth_augment_desc;
+/* in / out: device, [B][Hs][Ws] fp32, the same buffer or disjoint ones; Hs * Ws < 2^32.  state: device, state[0] is the step counter --
+ * the launch reads it and advances it by one (wrapping at 2^32), so a captured call draws fresh numbers at every replay.  params:
+ * device, 1 + 17 G ints (G = B, or `group`), receives [0] = the step used, then per stream count and four (top, left, h, w).
+ * rgb_params: null, or the table rpe_augment_frames_u8 wrote for the same batch with group == rgb_group (1 + 8 G ints, read only).
+ * Refused with RPE_ERR_SHAPE before any launch: a null pointer, a non-finite or negative n_i, q or inv_q, lo > hi or a NaN bound, a
+ * hole count outside 0 <= lo <= hi <= 4, rectangle bounds outside 1 <= lo <= hi <= Hs / Ws when hole_hi > 0, group < 0,
+ * Hs * Ws >= 2^32, rgb_group != group with rgb_params given, in and out overlapping without being equal.  16-byte loads and stores
+ * where both pointers are 16-byte aligned.  Two launches. */
+int rpe_augment_depth_f32(const float* in, float* out, int B, int Hs, int Ws, const rpe_depth_augment_desc* d, unsigned* state, int* params,
+                          const int* rgb_params, int rgb_group, void* stream);
+
 /* ------------------------------------------------------------------ batch norm */
 /* replaces: nn.BatchNorm2d (train mode: biased batch variance, eps, momentum with
  * unbiased running variance) + the in-place nn.ReLU and `out += identity` of the

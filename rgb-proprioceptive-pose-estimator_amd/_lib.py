@@ -54,6 +54,13 @@ class MeasureDesc(Structure):
     _fields_ = [("seed", ctypes.c_ulonglong)] + [(n, c_int) for n in ("S", "N", "num_scales")] + [("sigma", c_double * 8), ("rho", c_double)]
 
 
+class DepthAugmentDesc(Structure):
+    """rpe_depth_augment_desc"""
+    _fields_ = ([("seed", ctypes.c_ulonglong)] + [(n, c_double) for n in ("n0", "n1", "n2", "q", "inv_q", "lo", "hi")] + [("drop_thresh", ctypes.c_uint)]
+                + [(n, c_int) for n in ("hole_lo", "hole_hi", "hh_lo", "hh_hi", "hw_lo", "hw_hi")] + [("hole_value", c_float), ("occluder_value", c_float),
+                                                                                                       ("group", c_int)])
+
+
 class OcclusionDesc(Structure):
     """rpe_occlusion_desc"""
     _fields_ = [(n, c_int) for n in ("Hs", "Ws", "ph", "pw", "sy", "sx")] + [("fill_rgb", ctypes.c_ubyte * 3)]
@@ -121,6 +128,7 @@ _SPEC = {
     "rpe_stage_frames_u8_resized": (I, [I, P, P, I, I, I, I, I, I, I, I, I, P, P, I, P, P, I, P, POINTER(c_float), POINTER(c_float), P]),
     "rpe_stage_depth_f32_resized": (I, [P, P, I, I, I, I, I, I, I, I, I, P, P, I, P, P, I, P]),
     "rpe_augment_frames_u8": (I, [P, P, I, I, I, POINTER(AugmentDesc), P, P, P, P]),
+    "rpe_augment_depth_f32": (I, [P, P, I, I, I, POINTER(DepthAugmentDesc), P, P, P, I, P]),
     "rpe_sample_windows": (I, [POINTER(SampleDesc), P, P, P, P]),
     "rpe_gather_rows": (I, [P, P, L, L, P, I, I, P]),
     "rpe_measurement_noise": (I, [P, P, POINTER(MeasureDesc), P, P, P]),

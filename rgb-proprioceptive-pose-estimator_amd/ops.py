@@ -838,6 +838,80 @@ def augment_frames_u8(frames, desc, state, out=None, params=None, sums=None):
     return out
 
 
+DEPTH_AUGMENT_DESC_FIELDS = ("seed", "n0", "n1", "n2", "q", "inv_q", "lo", "hi", "drop_thresh", "hole_lo", "hole_hi", "hh_lo", "hh_hi", "hw_lo", "hw_hi",
+                             "hole_value", "occluder_value", "group")
+DEPTH_AUGMENT_DESC_NUMBERS = ("seed_lo", "seed_hi") + DEPTH_AUGMENT_DESC_FIELDS[1:]   # the flat list of torch.ops.rpe.augment_depth_f32
+DEPTH_AUGMENT_ROW = 17  # ints per stream in the parameter table: count, 4 x (top, left, h, w)
+
+
+def depth_augment_desc(seed=0, n0=0.0, n1=0.0, n2=0.0, q=0.0, inv_q=0.0, lo=-math.inf, hi=math.inf, drop_thresh=0, hole_lo=0, hole_hi=0, hh_lo=1, hh_hi=1,
+                       hw_lo=1, hw_hi=1, hole_value=0.0, occluder_value=0.0, group=0):
+    """rpe_depth_augment_desc from plain numbers (the defaults are the identity settings); DEPTH_AUGMENT_DESC_FIELDS is the order of
+    the flat list form `torch.ops.rpe.augment_depth_f32` takes.  n0..n2 are the kernel's coefficients, sigma_i / sqrt(2 (2^32 - 1))
+    (util.data_utils.DepthAugment converts); inv_q is 1 / q, computed by the caller in double."""
+    from ._lib import DepthAugmentDesc
+    d = DepthAugmentDesc()
+    d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    for k, v in (("n0", n0), ("n1", n1), ("n2", n2), ("q", q), ("inv_q", inv_q), ("lo", lo), ("hi", hi), ("hole_value", hole_value),
+                 ("occluder_value", occluder_value)):
+        setattr(d, k, float(v))
+    if not 0 <= int(drop_thresh) < 2 ** 32:
+        raise ValueError("depth_augment_desc: drop_thresh is an unsigned 32-bit word; got %r" % (drop_thresh,))
+    d.drop_thresh = int(drop_thresh)
+    for k, v in (("hole_lo", hole_lo), ("hole_hi", hole_hi), ("hh_lo", hh_lo), ("hh_hi", hh_hi), ("hw_lo", hw_lo), ("hw_hi", hw_hi), ("group", group)):
+        setattr(d, k, int(v))
+    return d
+
+
+def depth_frame_hw(shape):
+    """(Hs, Ws) of a depth batch of `shape`: channels-last (..., Hs, Ws, 1) as recorded, or (..., 1, H, W) as the synthetic dataset
+    hands it out -- both are [B][Hs][Ws] in memory.  A trailing 1 decides for channels-last."""
+    shape = tuple(shape)
+    if len(shape) >= 4 and shape[-1] == 1:
+        return shape[-3], shape[-2]
+    if len(shape) >= 4 and shape[-3] == 1:
+        return shape[-2], shape[-1]
+    raise ValueError("depth frames are (..., Hs, Ws, 1) or (..., 1, H, W); got %r" % (shape,))
+
+
+def augment_depth_f32(depth, desc, state, out=None, params=None, rgb_params=None, rgb_group=0):
+    """depth fp32 contiguous, [B][Hs][Ws] in memory: (..., Hs, Ws, 1) or (..., 1, H, W) -> the augmented depth, fp32 of the same shape
+    (rpe_augment_depth_f32: range noise, quantisation, clamp, dropout, holes, shared occluder).  desc: depth_augment_desc(...).
+    state: int32 device tensor whose element 0 is the step counter; the launch advances it by one.  out: destination (may be `depth`
+    itself).  params: int32 (1 + 17 G,) device tensor receiving the parameter table (allocated when not given).  rgb_params: the table
+    augment_frames_u8 wrote for the same batch with group `rgb_group` -- its erased rectangles become occluder_value here."""
+    if depth.dtype != torch.float32:
+        raise ValueError("augment_depth_f32: depth must be fp32 (..., Hs, Ws, 1) or (..., 1, H, W); got %s %r" % (depth.dtype, tuple(depth.shape)))
+    hs, ws = depth_frame_hw(depth.shape)
+    _chk(depth, "depth")
+    if hs * ws == 0 or depth.numel() == 0:
+        raise ValueError("augment_depth_f32: empty batch")
+    b = depth.numel() // (hs * ws)
+    g = augment_streams(desc, b)
+    dev = depth.device
+    if state.dtype != torch.int32 or state.numel() < 1 or state.device != dev:
+        raise ValueError("augment_depth_f32: state must be an int32 tensor on the depth frames' device")
+    if out is None:
+        out = torch.empty_like(depth)
+    elif out.dtype != torch.float32 or out.shape != depth.shape or out.device != dev:
+        raise ValueError("augment_depth_f32: out must be fp32 of the depth frames' shape on their device")
+    _chk(out, "out")
+    n = 1 + DEPTH_AUGMENT_ROW * g
+    if params is None:
+        params = torch.empty(n, dtype=torch.int32, device=dev)
+    elif params.dtype != torch.int32 or params.numel() < n or params.device != dev:
+        raise ValueError("augment_depth_f32: params must be int32 with at least %d elements" % n)
+    if rgb_params is not None:
+        if int(rgb_group) != desc.group:
+            raise ValueError("augment_depth_f32: the RGB table was drawn with group %d, the depth descriptor has %d" % (rgb_group, desc.group))
+        if rgb_params.dtype != torch.int32 or rgb_params.numel() < 1 + 8 * g or rgb_params.device != dev:
+            raise ValueError("augment_depth_f32: rgb_params must be int32 with at least %d elements on the depth frames' device" % (1 + 8 * g))
+        _chk(rgb_params, "rgb_params")
+    lib.rpe_augment_depth_f32(_p(depth), _p(out), b, hs, ws, ctypes.byref(desc), _p(_chk(state, "state")), _p(_chk(params, "params")),
+                              None if rgb_params is None else _p(rgb_params), int(rgb_group), _stream())
+    return out
+
+
 SAMPLE_DESC_FIELDS = ("seed", "E", "T", "S", "stride", "N", "shuffle")
 
 

@@ -9,7 +9,9 @@ Added flags: --dtype {bf16,f16,f32}, --optimizer {fused,torch}, --max_grad_norm,
 learning-rate schedule (--lr_schedule, --warmup_steps, --warmup_start_factor, --lr_total_steps, --lr_min_factor, --lr_step_size,
 --lr_gamma), --trunk_lr_scale (the trunk as a param group of its own) and --ema_decay (writes `<checkpoint>.ema` beside the raw weights);
 the on-device frame augmentation of recorded episodes (--aug_brightness, --aug_contrast, --aug_saturation, --aug_noise_std,
---aug_erase_prob, --aug_erase_scale, --aug_erase_fill, --aug_per_frame, --aug_seed; all off by default, they need --episodes);
+--aug_erase_prob, --aug_erase_scale, --aug_erase_fill, --aug_per_frame, --aug_seed; all off by default, they need --episodes) and of
+their depth frames (--aug_depth_noise, --aug_depth_drop_prob, --aug_depth_holes, --aug_depth_hole_scale, --aug_depth_hole_value,
+--aug_depth_quant, --aug_depth_clamp, --aug_depth_share_erase, --aug_depth_occluder_value; off by default, they need --use_depth --episodes);
 --resident (the --episodes file lives in HBM) and, with it, --batch_size, --window_stride, --shuffle_seed (shuffled minibatches drawn on the
 device instead of one chunk of every episode per step); --meas_noise_device / --meas_noise_scales, --meas_noise_correlation,
 --meas_noise_seed (the measurement noise of the `train` phase drawn on the device, fresh at every step; off by default, any dataset).
@@ -99,6 +101,21 @@ def build_parser():
     p.add_argument("--aug_per_frame", action="store_true",
                    help="augmentation: draw jitter and occluder per frame (default: per episode, kept through a chunk of --sequence_length steps)")
     p.add_argument("--aug_seed", type=int, default=None, help="augmentation: seed of the device generator (default 0; rank r uses seed + r)")
+    p.add_argument("--aug_depth_noise", type=float, nargs="+", default=None, metavar="S",
+                   help="depth augmentation (needs --use_depth --episodes): S0 [S1 [S2]], noise of standard deviation S0 + S1 d + S2 d^2 at depth d, "
+                        "in the units of the recorded depth values (default: off)")
+    p.add_argument("--aug_depth_drop_prob", type=float, default=None, metavar="P", help="depth augmentation: probability that a pixel becomes the hole value (default: off)")
+    p.add_argument("--aug_depth_holes", type=int, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="depth augmentation: LO..HI hole rectangles per frame, at most 4 (default 0 0: off)")
+    p.add_argument("--aug_depth_hole_scale", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="depth augmentation: each side of a hole as a fraction of the frame's (default 0.02 0.15)")
+    p.add_argument("--aug_depth_hole_value", type=float, default=None, metavar="V", help="depth augmentation: what dropped and hole pixels become (default 0)")
+    p.add_argument("--aug_depth_quant", type=float, default=None, metavar="Q", help="depth augmentation: round to multiples of Q (default: off)")
+    p.add_argument("--aug_depth_clamp", type=float, nargs=2, default=None, metavar=("LO", "HI"), help="depth augmentation: limit to [LO, HI] (default: off)")
+    p.add_argument("--aug_depth_share_erase", action="store_true",
+                   help="depth augmentation: the rectangle --aug_erase_prob erases in the RGB frame is covered in depth as well (needs --aug_erase_prob)")
+    p.add_argument("--aug_depth_occluder_value", type=float, default=None, metavar="V",
+                   help="depth augmentation: what the shared occluder writes (default 0)")
     p.add_argument("--resident", action="store_true",
                    help="keep the whole --episodes file in HBM (util.data_utils.ResidentEpisodeDataset): batches are gathered on the device, no PCIe per step")
     p.add_argument("--batch_size", type=int, default=None,
@@ -192,6 +209,38 @@ def build_augment(args, rank=0):
         raise SystemExit("--aug_*: %s" % e)
 
 
+DEPTH_AUGMENT_FLAGS = ("aug_depth_noise", "aug_depth_drop_prob", "aug_depth_holes", "aug_depth_hole_scale", "aug_depth_hole_value", "aug_depth_quant",
+                       "aug_depth_clamp", "aug_depth_occluder_value")
+
+
+def build_depth_augment(args, rank=0, augment=None):
+    """the --aug_depth_* family -> util.data_utils.DepthAugment, or None when none of its flags is given.  The flags need --use_depth
+    (a model that reads depth) and --episodes (recorded depth frames); --aug_depth_share_erase needs --aug_erase_prob and takes
+    `augment`, the FrameAugment of the same rank (build_augment).  --aug_per_frame and --aug_seed hold for depth as for RGB."""
+    from rgb_proprioceptive_pose_estimator_amd.util.data_utils import DepthAugment
+    given = {k: getattr(args, k, None) for k in DEPTH_AUGMENT_FLAGS}
+    share = bool(getattr(args, "aug_depth_share_erase", False))
+    if all(v is None for v in given.values()) and not share:
+        return None
+    if not getattr(args, "use_depth", False):
+        raise SystemExit("the --aug_depth_* flags need --use_depth: without it the model does not read depth")
+    if not getattr(args, "episodes", None):
+        raise SystemExit("the --aug_depth_* flags need --episodes: the augmentation works on recorded depth frames")
+    if share and (getattr(args, "aug_erase_prob", None) is None or augment is None):
+        raise SystemExit("--aug_depth_share_erase needs --aug_erase_prob: it covers in depth the rectangle the RGB augmentation erases")
+    noise = given["aug_depth_noise"] or [0.0]
+    if len(noise) > 3:
+        raise SystemExit("--aug_depth_noise takes one to three coefficients S0 [S1 [S2]]; got %d" % len(noise))
+    try:
+        return DepthAugment(noise=tuple(noise), drop_prob=given["aug_depth_drop_prob"] or 0.0, holes=tuple(given["aug_depth_holes"] or (0, 0)),
+                            hole_scale=tuple(given["aug_depth_hole_scale"] or (0.02, 0.15)), hole_value=given["aug_depth_hole_value"] or 0.0,
+                            quant=given["aug_depth_quant"] or 0.0, clamp=None if given["aug_depth_clamp"] is None else tuple(given["aug_depth_clamp"]),
+                            occluder_value=given["aug_depth_occluder_value"] or 0.0, per_frame=bool(getattr(args, "aug_per_frame", False)),
+                            seed=(getattr(args, "aug_seed", None) or 0) + rank, share_erase=augment if share else None)
+    except ValueError as e:
+        raise SystemExit("--aug_depth_*: %s" % e)
+
+
 DTYPES = {"bf16": torch.bfloat16, "f16": torch.float16, "f32": torch.float32}
 
 
@@ -276,7 +325,7 @@ def build_optimizer(args, params):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    build_augment(args)   # (a flag that cannot be honoured stops the run before anything is built)
+    build_depth_augment(args, augment=build_augment(args))   # (a flag that cannot be honoured stops the run before anything is built)
     sampling = build_sampling(args)
     build_measurement_noise(args)
     from rgb_proprioceptive_pose_estimator_amd.dist import init_from_env
@@ -317,10 +366,11 @@ def main(argv=None):
     if rank == 0:
         print("Training...")
     telemetry_log = [] if args.telemetry_out is not None else None
+    augment = build_augment(args, rank)
     result = train(model=model, dataset=dataset, criterion=criterion, optimizer=optimizer, num_epochs=args.n_epochs,
                    num_train_episodes_per_epoch=args.n_train_episodes_per_epoch, num_val_episodes_per_epoch=args.n_val_episodes_per_epoch,
-                   params=params, device=device, save_model=not args.no_save, augment=build_augment(args, rank),
-                   measurement_noise=build_measurement_noise(args, rank), telemetry=args.telemetry, telemetry_log=telemetry_log, **sampling)
+                   params=params, device=device, save_model=not args.no_save, augment=augment,
+                   depth_augment=build_depth_augment(args, rank, augment), measurement_noise=build_measurement_noise(args, rank), telemetry=args.telemetry, telemetry_log=telemetry_log, **sampling)
     if telemetry_log and rank == 0:
         save_telemetry(args.telemetry_out, telemetry_log)
     return result

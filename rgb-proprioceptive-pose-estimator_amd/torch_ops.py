@@ -18,6 +18,7 @@ ResNet; models/losses.py:114-128 is the loss; util/learn_utils.py:152-184 the st
     rpe::adam_step                                  torch.optim.Adam's update of one flat fp32 tensor, in place
     rpe::param_stats                                torch._foreach_norm over gradients and parameters, isfinite / zero counts and the update norm per tensor, two launches
     rpe::augment_frames_u8                          (no counterpart: the reference does not augment) jitter, noise and erasing of raw uint8 frames
+    rpe::augment_depth_f32                          (no counterpart) depth-sensor model on raw fp32 depth: range noise, quantisation, clamp, dropout, holes, the RGB occluder
     rpe::sample_windows / gather_rows               DataLoader(shuffle=True) over episode windows resident in HBM: the batch's index, and its rows
     rpe::measurement_noise                          x0 + sqrt(scale) * randn_like(x0) with the quaternion renormalised (util/data_utils.py:162-167), drawn on the device
     rpe::occlude_grid_u8 / pose_displacement /      (no counterpart: occlusion sensitivity) a frame with one rectangle of a grid covered per row; how far
@@ -35,7 +36,7 @@ import torch
 __all__ = ["NAMES"]
 
 _NS = "rpe"
-NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step", "augment_frames_u8", "sample_windows", "gather_rows",
+NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step", "augment_frames_u8", "augment_depth_f32", "sample_windows", "gather_rows",
          "measurement_noise", "occlude_grid_u8", "pose_displacement", "saliency_map", "saliency_overlay_u8", "param_stats", "project_poses", "draw_poses_u8")
 
 
@@ -213,6 +214,26 @@ def augment_frames_u8(frames: torch.Tensor, desc: List[int], state: torch.Tensor
 @augment_frames_u8.register_fake
 def _(frames, desc, state):
     return torch.empty_like(frames)
+
+
+@torch.library.custom_op(_NS + "::augment_depth_f32", mutates_args=("state",), device_types="cuda")
+def augment_depth_f32(depth: torch.Tensor, desc: List[float], state: torch.Tensor, rgb_params: Optional[torch.Tensor] = None, rgb_group: int = 0) -> torch.Tensor:
+    """depth fp32 (..., Hs, Ws, 1) or (..., 1, H, W) -> augmented fp32 depth; desc: the numbers of ops.DEPTH_AUGMENT_DESC_NUMBERS (the
+    seed as two 32-bit words, then the fields of rpe_depth_augment_desc); state: int32, element 0 is the step counter, advanced by
+    one; rgb_params / rgb_group: the table rpe::augment_frames_u8's launch wrote for the same batch, for the shared occluder"""
+    ops = _ops()
+    if len(desc) != len(ops.DEPTH_AUGMENT_DESC_NUMBERS):
+        raise ValueError("augment_depth_f32: desc has %d numbers (%s)" % (len(ops.DEPTH_AUGMENT_DESC_NUMBERS), ", ".join(ops.DEPTH_AUGMENT_DESC_NUMBERS)))
+    lo, hi = int(desc[0]), int(desc[1])
+    if not (0 <= lo < 2 ** 32 and 0 <= hi < 2 ** 32):
+        raise ValueError("augment_depth_f32: the seed travels as two 32-bit words; got %r, %r" % (desc[0], desc[1]))
+    fields = dict(zip(ops.DEPTH_AUGMENT_DESC_FIELDS[1:], desc[2:]))
+    return ops.augment_depth_f32(depth, ops.depth_augment_desc(seed=lo | (hi << 32), **fields), state, rgb_params=rgb_params, rgb_group=rgb_group)
+
+
+@augment_depth_f32.register_fake
+def _(depth, desc, state, rgb_params=None, rgb_group=0):
+    return torch.empty_like(depth)
 
 
 # ---- minibatch sampling from resident episodes ---------------------------------------------------------------------------------

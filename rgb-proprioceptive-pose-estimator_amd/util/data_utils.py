@@ -9,9 +9,10 @@ episodes at timestep t, util/data_utils.py:62-73), the 6-tuple, `refresh_data`, 
 proprioception = truth + N(0, noise_scale I) with the quaternion renormalised, util/data_utils.py:162-176),
 generated directly in HBM.  RecordedEpisodeDataset reads episodes recorded from the simulator elsewhere back from a file, raw, and
 leaves every image transform to the device; ResidentEpisodeDataset keeps that file in HBM and WindowSampler draws shuffled minibatches
-from it on the device.  FrameAugment and MeasurementNoise draw what varies between train steps -- the frame augmentation and the
-measurement noise -- on the device as well, keyed by (seed, step).
+from it on the device.  FrameAugment, DepthAugment and MeasurementNoise draw what varies between train steps -- the frame and depth
+augmentation and the measurement noise -- on the device as well, keyed by (seed, step).
 """
+import math
 import types
 
 import torch
@@ -458,7 +459,35 @@ def _jitter_range(name, amount):
     return _q16(max(0.0, 1.0 - a)), _q16(1.0 + a)
 
 
-class FrameAugment:
+class _DeviceStepCounter:
+    """What FrameAugment, DepthAugment and MeasurementNoise share: `seed`, and a step counter that lives in device memory once the
+    object has run (`_state`, an int32 tensor whose element 0 the launch itself advances) and on the host before that (`_step0`)."""
+
+    def _device_state(self, device):
+        if self._state is None or self._state.device != device:
+            step = self.step
+            self._state = torch.tensor([step - (1 << 32) if step >= (1 << 31) else step], dtype=torch.int32, device=device)
+        return self._state
+
+    @property
+    def step(self):
+        """the step counter: the number of calls so far, replays of a captured call included (reads the device)"""
+        return self._step0 if self._state is None else int(self._state[0].item()) & 0xFFFFFFFF
+
+    def state_dict(self):
+        return {"seed": self.seed, "step": self.step}
+
+    def load_state_dict(self, sd):
+        seed, step = int(sd["seed"]), int(sd["step"])
+        if not (0 <= seed < 2 ** 64 and 0 <= step < 2 ** 32):
+            raise ValueError("{}.load_state_dict: seed / step out of range: {!r}".format(type(self).__name__, sd))
+        self.seed = seed
+        self._step0 = step
+        if self._state is not None:   # in place: a captured call keeps reading this tensor
+            self._state.fill_(step - (1 << 32) if step >= (1 << 31) else step)
+
+
+class FrameAugment(_DeviceStepCounter):
     """Label-preserving augmentation of raw uint8 camera frames on the device (rpe_augment_frames_u8; DESIGN.md "Frame
     augmentation"): brightness / contrast / saturation jitter with torchvision's ranges (`brightness=b`: a factor in
     [max(0, 1 - b), 1 + b]), sensor noise of `noise_std` grey levels, and random erasing of one rectangle per frame with probability
@@ -507,6 +536,7 @@ class FrameAugment:
         if not 0 <= self.seed < 2 ** 64:
             raise ValueError("seed must fit 64 unsigned bits; got {!r}".format(seed))
         self.last_params = None     # device table of the last call: [0] the step used, then per stream qb qc qs erase top left h w
+        self.last_geometry = None   # (Hs, Ws, frames, group) of the last call
         self._state = None          # int32 device tensor, element 0 = the step counter
         self._step0 = 0             # the counter while there is no device tensor yet
         self._buffers = {}
@@ -533,12 +563,6 @@ class FrameAugment:
         if not frames.is_cuda:
             raise ValueError("FrameAugment runs on the device only (there is no CPU path); got a {} tensor".format(frames.device))
 
-    def _device_state(self, device):
-        if self._state is None or self._state.device != device:
-            step = self.step
-            self._state = torch.tensor([step - (1 << 32) if step >= (1 << 31) else step], dtype=torch.int32, device=device)
-        return self._state
-
     def __call__(self, frames, out=None):
         from .. import ops
         self.check_frames(frames)
@@ -553,27 +577,151 @@ class FrameAugment:
         params, sums = self._buffers[key]
         out = ops.augment_frames_u8(frames, ops.augment_desc(**self.desc_fields(hs, ws, group)), state, out=out, params=params, sums=sums)
         self.last_params = params
+        self.last_geometry = (int(hs), int(ws), int(b), int(group))   # what DepthAugment(share_erase=self) checks its own batch against
         return out
 
-    @property
-    def step(self):
-        """the step counter: the number of calls so far, replays of a captured call included (reads the device)"""
-        return self._step0 if self._state is None else int(self._state[0].item()) & 0xFFFFFFFF
-
-    def state_dict(self):
-        return {"seed": self.seed, "step": self.step}
-
-    def load_state_dict(self, sd):
-        seed, step = int(sd["seed"]), int(sd["step"])
-        if not (0 <= seed < 2 ** 64 and 0 <= step < 2 ** 32):
-            raise ValueError("FrameAugment.load_state_dict: seed / step out of range: {!r}".format(sd))
-        self.seed = seed
-        self._step0 = step
-        if self._state is not None:   # in place: a captured call keeps reading this tensor
-            self._state.fill_(step - (1 << 32) if step >= (1 << 31) else step)
 
 
-class MeasurementNoise:
+DEPTH_NOISE_T_STD = math.sqrt(2.0 * (2 ** 32 - 1))   # standard deviation of the kernel's integer T: Var T = 4 * 6 * (65536^2 - 1) / 12
+
+
+class DepthAugment(_DeviceStepCounter):
+    """Depth-sensor augmentation of raw fp32 depth frames on the device (rpe_augment_depth_f32; DESIGN.md "Depth augmentation"), the
+    depth side of FrameAugment.  Per pixel d, in this order:
+      noise=(s0, s1, s2): d + N(0, sd^2) with sd = s0 + s1 d + s2 d^2 -- constant, linear and quadratic in range, in the units of the
+          recorded depth values (robosuite: the normalised z-buffer); one or two values set the leading coefficients
+      quant=q: rounded to multiples of q (round half even)
+      clamp=(lo, hi): limited to [lo, hi]
+      drop_prob=p: the pixel becomes `hole_value` with probability p
+      holes=(lo, hi): lo..hi rectangles per frame (at most 4), each side a fraction `hole_scale` = (lo, hi) of the frame's, set to
+          `hole_value`
+      share_erase=<the FrameAugment of the RGB frames>: the rectangle that augmentation erased in a frame becomes `occluder_value`
+          here, so that the occluder hides depth as well; call it on the RGB frames of the batch FIRST
+    No crop, shift, flip or global rescale: the labels are absolute poses seen by a fixed camera.  The random numbers are drawn on the
+    device from (seed, step) under purposes of their own, so one seed given to FrameAugment and DepthAugment yields independent draws;
+    the step counter lives in device memory and every call advances it, also a call replayed from a captured graph.
+    per_frame=False: frames (S, N, ...) share their holes along S (one episode keeps them through the chunk) -- the grouping
+    FrameAugment(per_episode=True) uses; noise and dropout are always per frame and per pixel.  A 4-D batch draws per frame.
+    Takes contiguous fp32 device tensors (..., Hs, Ws, 1), as recorded, or (..., 1, H, W), as the synthetic dataset hands them out.
+
+        daug = DepthAugment(noise=(0.001, 0.0, 0.002), drop_prob=0.01, holes=(0, 2), share_erase=aug)
+        frames = aug(frames); depth = daug(depth)      # a new fp32 tensor of the same shape
+    """
+
+    def __init__(self, noise=(0., 0., 0.), drop_prob=0., holes=(0, 0), hole_scale=(0.02, 0.15), hole_value=0., quant=0., clamp=None, occluder_value=0.,
+                 per_frame=False, seed=0, share_erase=None):
+        try:
+            sig = tuple(float(v) for v in (noise if isinstance(noise, (tuple, list)) else (noise,)))
+        except (TypeError, ValueError):
+            sig = ()
+        if not 1 <= len(sig) <= 3 or not all(math.isfinite(v) and v >= 0.0 for v in sig):
+            raise ValueError("noise is one to three finite, non-negative standard-deviation coefficients (s0, s1, s2); got {!r}".format(noise))
+        self.noise = sig + (0.0,) * (3 - len(sig))
+        self.n = tuple(v / DEPTH_NOISE_T_STD for v in self.noise)   # in double: the kernel never sees a square root
+        if not 0.0 <= float(drop_prob) <= 1.0:
+            raise ValueError("drop_prob must lie in [0, 1]; got {!r}".format(drop_prob))
+        self.drop_thresh = min(2 ** 32 - 1, int(round(float(drop_prob) * 2 ** 32)))
+        try:
+            h_lo, h_hi = (int(v) for v in holes)
+        except (TypeError, ValueError):
+            raise ValueError("holes is (lo, hi), the number of rectangles per frame; got {!r}".format(holes))
+        if not 0 <= h_lo <= h_hi <= 4:
+            raise ValueError("holes must be (lo, hi) with 0 <= lo <= hi <= 4; got {!r}".format(holes))
+        self.holes = (h_lo, h_hi)
+        lo, hi = (float(v) for v in hole_scale)
+        if not 0.0 < lo <= hi <= 1.0:
+            raise ValueError("hole_scale must be (lo, hi) with 0 < lo <= hi <= 1; got {!r}".format(hole_scale))
+        self.hole_scale = (lo, hi)
+        self.quant = float(quant)
+        if not (math.isfinite(self.quant) and self.quant >= 0.0):
+            raise ValueError("quant must be finite and not negative; got {!r}".format(quant))
+        self.inv_quant = 1.0 / self.quant if self.quant > 0.0 else 0.0
+        if not math.isfinite(self.inv_quant):
+            raise ValueError("quant {!r} is too small: 1 / quant is not finite".format(quant))
+        if clamp is None:
+            self.clamp = (-math.inf, math.inf)
+        else:
+            lo, hi = (float(v) for v in clamp)
+            if not lo <= hi:   # (false for a NaN as well)
+                raise ValueError("clamp must be (lo, hi) with lo <= hi; got {!r}".format(clamp))
+            self.clamp = (lo, hi)
+        self.hole_value, self.occluder_value = float(hole_value), float(occluder_value)
+        self.per_frame = bool(per_frame)
+        self.seed = int(seed)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must fit 64 unsigned bits; got {!r}".format(seed))
+        if share_erase is not None and not isinstance(share_erase, FrameAugment):
+            raise ValueError("share_erase takes the FrameAugment of the RGB frames; got {!r}".format(type(share_erase).__name__))
+        self.share_erase = share_erase
+        self.last_params = None     # device table of the last call: [0] the step used, then per stream count and 4 x (top, left, h, w)
+        self._state = None          # int32 device tensor, element 0 = the step counter
+        self._step0 = 0             # the counter while there is no device tensor yet
+        self._buffers = {}
+
+    def hole_bounds(self, size):
+        """hole_scale as pixel bounds (lo, hi) of a side of `size` pixels, 1 <= lo <= hi <= size"""
+        lo = min(size, max(1, int(round(self.hole_scale[0] * size))))
+        return lo, min(size, max(lo, int(round(self.hole_scale[1] * size))))
+
+    def desc_fields(self, hs, ws, group=0):
+        """the arguments of ops.depth_augment_desc for frames of hs x ws"""
+        (hh_lo, hh_hi), (hw_lo, hw_hi) = self.hole_bounds(hs), self.hole_bounds(ws)
+        return dict(seed=self.seed, n0=self.n[0], n1=self.n[1], n2=self.n[2], q=self.quant, inv_q=self.inv_quant, lo=self.clamp[0], hi=self.clamp[1],
+                    drop_thresh=self.drop_thresh, hole_lo=self.holes[0], hole_hi=self.holes[1], hh_lo=hh_lo, hh_hi=hh_hi, hw_lo=hw_lo, hw_hi=hw_hi,
+                    hole_value=self.hole_value, occluder_value=self.occluder_value, group=int(group))
+
+    @staticmethod
+    def check_depth(depth):
+        """ValueError unless `depth` is a contiguous fp32 device tensor (B, Hs, Ws, 1) / (S, N, Hs, Ws, 1) or (B, 1, H, W) / (S, N, 1, H, W);
+        -> (Hs, Ws)"""
+        from ..ops import depth_frame_hw
+        if not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32:
+            raise ValueError("DepthAugment takes fp32 depth frames; got {}".format(getattr(depth, "dtype", type(depth))))
+        if depth.dim() not in (4, 5) or not depth.is_contiguous() or depth.numel() == 0:
+            raise ValueError("DepthAugment takes depth frames (B, Hs, Ws, 1) / (S, N, Hs, Ws, 1) or (B, 1, H, W) / (S, N, 1, H, W), contiguous; got {}".format(
+                tuple(depth.shape)))
+        hw = depth_frame_hw(depth.shape)
+        if not depth.is_cuda:
+            raise ValueError("DepthAugment runs on the device only (there is no CPU path); got a {} tensor".format(depth.device))
+        return hw
+
+    def group_of(self, shape):
+        """the `group` of a batch of `shape`: N for windows (S, N, ...) unless per_frame, else 0"""
+        return int(shape[1]) if not self.per_frame and len(shape) == 5 else 0
+
+    def shared_table(self, hs, ws, b, group):
+        """(rgb_params, rgb_group) of the launch: the table share_erase's last call wrote, checked against this batch's geometry and
+        grouping; (None, 0) without share_erase"""
+        aug = self.share_erase
+        if aug is None:
+            return None, 0
+        if aug.last_params is None:
+            raise ValueError("DepthAugment(share_erase=...): the FrameAugment has not run yet -- augment the RGB frames of the batch first")
+        seen = getattr(aug, "last_geometry", None)
+        if seen != (int(hs), int(ws), int(b), int(group)):
+            raise ValueError("DepthAugment(share_erase=...): the RGB augmentation saw (Hs, Ws, frames, group) = {!r}, the depth frames are {!r}: "
+                             "the two must see the same geometry and grouping".format(seen, (int(hs), int(ws), int(b), int(group))))
+        return aug.last_params, int(group)
+
+    def __call__(self, depth, out=None):
+        from .. import ops
+        hs, ws = self.check_depth(depth)
+        group = self.group_of(depth.shape)
+        b = depth.numel() // (hs * ws)
+        rgb_params, rgb_group = self.shared_table(hs, ws, b, group)
+        state = self._device_state(depth.device)
+        key = (b, group, depth.device)
+        if key not in self._buffers:   # kept: a captured call has its address
+            self._buffers[key] = torch.empty(1 + ops.DEPTH_AUGMENT_ROW * (group or b), dtype=torch.int32, device=depth.device)
+        params = self._buffers[key]
+        out = ops.augment_depth_f32(depth, ops.depth_augment_desc(**self.desc_fields(hs, ws, group)), state, out=out, params=params,
+                                    rgb_params=rgb_params, rgb_group=rgb_group)
+        self.last_params = params
+        return out
+
+
+
+class MeasurementNoise(_DeviceStepCounter):
     """The measurement of the robot's own pose, x0bar = x0 + N(0, scale I) with the quaternion renormalised (what `refresh_data`
     draws on the host once per refresh, util/data_utils.py:162-167 of the reference), drawn on the device at EVERY call
     (rpe_measurement_noise; DESIGN.md "Measurement noise").  `scale` is a variance, as `noise_scale` is, or a sequence of 1..8
@@ -615,12 +763,6 @@ class MeasurementNoise:
         """the arguments of ops.measure_desc for S = s timesteps of N = n lanes"""
         return dict(seed=self.seed, S=int(s), N=int(n), scales=self.scales, correlation=self.correlation)
 
-    def _device_state(self, device):
-        if self._state is None or self._state.device != device:
-            step = self.step
-            self._state = torch.tensor([step - (1 << 32) if step >= (1 << 31) else step], dtype=torch.int32, device=device)
-        return self._state
-
     def __call__(self, x0, out=None):
         from .. import ops
         s, n = self.check_poses(x0)
@@ -635,22 +777,6 @@ class MeasurementNoise:
         self.last_picks = self._picks
         return out
 
-    @property
-    def step(self):
-        """the step counter: the number of calls so far, replays of a captured call included (reads the device)"""
-        return self._step0 if self._state is None else int(self._state[0].item()) & 0xFFFFFFFF
-
-    def state_dict(self):
-        return {"seed": self.seed, "step": self.step}
-
-    def load_state_dict(self, sd):
-        seed, step = int(sd["seed"]), int(sd["step"])
-        if not (0 <= seed < 2 ** 64 and 0 <= step < 2 ** 32):
-            raise ValueError("MeasurementNoise.load_state_dict: seed / step out of range: {!r}".format(sd))
-        self.seed = seed
-        self._step0 = step
-        if self._state is not None:   # in place: a captured call keeps reading this tensor
-            self._state.fill_(step - (1 << 32) if step >= (1 << 31) else step)
 
 
 class FramePrefetcher:

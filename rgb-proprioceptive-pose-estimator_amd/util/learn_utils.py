@@ -131,7 +131,8 @@ class GraphedTrainStep:
         loss, pos_err, ori_err = step()               # ... and fresh measurement noise on its true poses
     """
 
-    def __init__(self, model, criterion, optimizer, train_obj_pose, example_batch, warmup=3, augment=None, sampler=None, measurement_noise=None):
+    def __init__(self, model, criterion, optimizer, train_obj_pose, example_batch, warmup=3, augment=None, sampler=None, measurement_noise=None,
+                 depth_augment=None):
         if dist.is_initialized() and dist.get_world_size() > 1:
             raise RuntimeError("GraphedTrainStep is single-process; data-parallel steps run eagerly")
         if not getattr(optimizer, "capturable", False):
@@ -166,6 +167,16 @@ class GraphedTrainStep:
         if measurement_noise is not None:
             measurement_noise.check_poses(self.static[3])
             self.fed = self.fed[:2] + (torch.empty_like(self.static[3]),) + self.fed[3:]
+        # depth_augment (util.data_utils.DepthAugment): inside the captured step as well, AFTER `augment`, so that the RGB table of the
+        # same step exists where the two share the occluder -- it reads the static raw depth and writes a buffer of its own, which takes
+        # the place of fed[1].  Its counter lives on the device and advances with every replay (and with the warm-up steps).
+        self.depth_augment = depth_augment
+        if depth_augment is not None:
+            _check_depth_augment(depth_augment, model, augment)
+            if self.static[1] is None:
+                raise ValueError("GraphedTrainStep(depth_augment=...) needs a batch with depth frames")
+            depth_augment.check_depth(self.static[1])
+            self.fed = self.fed[:1] + (torch.empty_like(self.static[1]),) + self.fed[2:]
 
         def step():
             if sampler is not None:
@@ -174,6 +185,8 @@ class GraphedTrainStep:
                 measurement_noise(self.static[3], out=self.fed[2])
             if augment is not None:
                 augment(self.static[0], out=self.fed[0])
+            if depth_augment is not None:
+                depth_augment(self.static[1], out=self.fed[1])
             return train_step(model, self.fed, criterion, optimizer, train_obj_pose, "train", None)
 
         model.train()
@@ -615,9 +628,21 @@ def telemetry_report(optimizer, model, host=None):
     return report
 
 
+def _check_depth_augment(depth_augment, model, augment):
+    """ValueError unless `depth_augment` is a DepthAugment that this model and this call's `augment` can honour"""
+    from .data_utils import DepthAugment
+    if not isinstance(depth_augment, DepthAugment):
+        raise ValueError("depth_augment=... takes a util.data_utils.DepthAugment; got {!r}".format(type(depth_augment).__name__))
+    if not getattr(model, "use_depth", False):
+        raise ValueError("depth_augment=... needs a model built with use_depth; {} does not read depth".format(type(model).__name__))
+    if depth_augment.share_erase is not None and depth_augment.share_erase is not augment:
+        raise ValueError("depth_augment.share_erase must be the FrameAugment given as augment=... to the same call: the occluder is shared "
+                         "with the RGB frames of the same step")
+
+
 def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_per_epoch, num_val_episodes_per_epoch, params, device,
           save_path='default', save_model=True, logging=True, *, save_optimizer=False, augment=None, batch_size=None, window_stride=None,
-          shuffle_seed=0, measurement_noise=None, telemetry=None, telemetry_log=None):
+          shuffle_seed=0, measurement_noise=None, telemetry=None, telemetry_log=None, depth_augment=None):
     """See the module docstring.  Returns (model with the best validation weights, best validation loss).
     save_optimizer (addition; the reference saves weights only): also write `<save_path>.optim` with the optimizer state of the
     best-validation epoch so that a run can be resumed (`optimizer.load_state_dict(torch.load(path))`).
@@ -637,6 +662,10 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
     measurement_noise (util.data_utils.MeasurementNoise): in the `train` phase the model is fed measurement_noise(x0), drawn on the
     device afresh at every step, in place of the dataset's x0bar (drawn on the host once per refresh); it needs the batch's x0 rows
     only, so every dataset takes it.  The `val` phase keeps the dataset's measurements, and the dataset's own pool is not written.
+    depth_augment (util.data_utils.DepthAugment): applied on the device to the depth frames of the `train` phase, AFTER `augment`, so
+    that the RGB table of the same step exists where the two share the occluder; the `val` phase sees the recorded depth and the
+    dataset's own depth is not written.  A ValueError for a model without use_depth, or when its share_erase names a FrameAugment
+    that is not the `augment` of this call.
     telemetry (None or K >= 1; needs FusedAdam(telemetry=K) with the same K): at the end of every `train` phase the optimizer's
     per-tensor table of the last measured step is read WITH the phase's one host read (no synchronisation per step is added) and
     written as Telemetry/grad_norm/<name>, Telemetry/update_ratio/<name>, Telemetry/zero_frac/<name>; when a tensor has seen
@@ -651,6 +680,8 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
         from .data_utils import MeasurementNoise
         if not isinstance(measurement_noise, MeasurementNoise):
             raise ValueError("train(measurement_noise=...) takes a util.data_utils.MeasurementNoise; got {!r}".format(type(measurement_noise).__name__))
+    if depth_augment is not None:
+        _check_depth_augment(depth_augment, model, augment)
     if batch_size is not None and not hasattr(dataset, "sampler"):
         raise ValueError("train(batch_size=...) draws minibatches on the device and needs a dataset with sampler() (ResidentEpisodeDataset); "
                          "{} has none".format(type(dataset).__name__))
@@ -722,6 +753,10 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
                         if img.dtype != torch.uint8:
                             raise ValueError("train(augment=...) needs raw uint8 frames; the dataset hands out {} images".format(img.dtype))
                         img = augment(img)
+                    if depth_augment is not None and phase == "train":   # after `augment`: the RGB table of this step exists
+                        if depth is None:
+                            raise ValueError("train(depth_augment=...): the dataset hands out no depth frames")
+                        depth = depth_augment(depth.contiguous())   # a new tensor: the dataset's own depth is not written
                     if measurement_noise is not None and phase == "train":
                         x0bar = measurement_noise(x0.contiguous())
                     loss, pe, oe = train_step(model, (img, depth, x0bar, x0, x1, obj), criterion, optimizer, train_obj_pose, phase, grad_sync)
