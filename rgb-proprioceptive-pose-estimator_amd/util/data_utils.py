@@ -10,11 +10,11 @@ proprioception = truth + N(0, noise_scale I) with the quaternion renormalised, u
 generated directly in HBM.  RecordedEpisodeDataset reads episodes recorded from the simulator elsewhere back from a file, raw, and
 leaves every image transform to the device; ResidentEpisodeDataset keeps that file in HBM and WindowSampler draws shuffled minibatches
 from it on the device.  FrameAugment, DepthAugment and MeasurementNoise draw what varies between train steps -- the frame and depth
-augmentation and the measurement noise -- on the device as well, keyed by (seed, step).
+augmentation and the measurement noise -- on the device as well, keyed by (seed, step); TrainInputs runs the four in front of the model.
 """
 import math
-import types
 
+import numpy as np
 import torch
 from torch.utils.data import Dataset
 
@@ -31,8 +31,6 @@ def pil_bilinear_tables(in_size, out_size):
     util/data_utils.py:48-54 of the reference): (bounds [out, 2] int32 = first input index and tap count, weights [out, ksize]
     int32 in 22-bit fixed point).  Host side, double precision, exactly Pillow's arithmetic (Resample.c precompute_coeffs +
     normalize_coeffs_8bpc); the device kernels only multiply-accumulate with them (csrc/norm.hip resize_*_kernel)."""
-    import math
-    import numpy as np
     scale = filterscale = in_size / out_size
     if filterscale < 1.0:
         filterscale = 1.0
@@ -59,8 +57,6 @@ def pil_bilinear_tables_f64(in_size, out_size):
     `pil_bilinear_tables`, weights [out, ksize] float64).  Resample.c precompute_coeffs, operation for operation: the filter argument
     is MULTIPLIED by 1 / filterscale, and the weights are summed in ascending tap order before the division -- the device kernel
     (csrc/depth_stage.hip) reproduces Pillow's pixels bit for bit only from bit-identical weights."""
-    import math
-    import numpy as np
     scale = filterscale = in_size / out_size
     if filterscale < 1.0:
         filterscale = 1.0
@@ -110,6 +106,14 @@ def random_poses(lead, generator, device):
     return torch.cat([pos, q], dim=-1)
 
 
+def noisy_measurement(x0, scale, z):
+    """measurement = truth + sqrt(scale) z, the quaternion part renormalised (util/data_utils.py:162-167 of the reference): x0 (..., 7)
+    true poses, `scale` a variance, z a standard-normal draw of x0's shape"""
+    xb = x0 + (scale ** 0.5) * z
+    q = xb[..., 3:]
+    return torch.cat([xb[..., :3], q / q.norm(dim=-1, keepdim=True)], dim=-1)
+
+
 def synthetic_batch(lead, seed, hw=224, with_depth=False, noise_scale=0.001, device="cuda"):
     """Seeded Robosuite-shaped batch with leading dims `lead` ((N,) or (S, N)), created on `device`."""
     lead = tuple(lead)
@@ -120,13 +124,29 @@ def synthetic_batch(lead, seed, hw=224, with_depth=False, noise_scale=0.001, dev
     img = (u8.float() / 255.0 - mean) / std
     depth = torch.rand(*lead, 1, hw, hw, generator=g, device=device) if with_depth else None
     x0, x1, obj = (random_poses(lead, g, device) for _ in range(3))
-    x0bar = x0 + (noise_scale ** 0.5) * torch.randn(*lead, 7, generator=g, device=device)
-    qb = x0bar[..., 3:]
-    x0bar = torch.cat([x0bar[..., :3], qb / qb.norm(dim=-1, keepdim=True)], dim=-1)
+    x0bar = noisy_measurement(x0, noise_scale, torch.randn(*lead, 7, generator=g, device=device))
     return {"img": img, "depth": depth, "x0bar": x0bar, "x0": x0, "x1": x1, "obj": obj}
 
 
-class SyntheticEpisodeDataset(Dataset):
+class _TimestepItems(Dataset):
+    """`len()` = the horizon and `dataset[t]` = the reference's 6-tuple of all episodes at timestep t (util/data_utils.py:62-73), read
+    from `self.data`; fields the dataset does not have are torch.empty garbage, as in the reference"""
+
+    def __len__(self):
+        return self.data["measurement_self"].size(1)
+
+    def __getitem__(self, index):
+        d = self.data
+        img = d["imgs"][:, index]
+        depth = d["depths"][:, index] if self.use_depth else torch.empty(0, device=img.device)
+        x0bar = d["measurement_self"][:, index]
+        x0 = d["true_self"][:, index]
+        x1 = d["true_other"][:, index] if self.is_two_arm else torch.empty_like(x0)
+        obj = d["true_obj"][:, index] if self.obj_name is not None else torch.empty_like(x0)
+        return img, depth, x0bar, x0, x1, obj
+
+
+class SyntheticEpisodeDataset(_TimestepItems):
     """MultiEpisodeDataset-shaped source of seeded synthetic episodes, resident on `device`."""
 
     frame_dtype = torch.float32   # preprocessed (normalised) images: nothing for FrameAugment to work on
@@ -146,19 +166,6 @@ class SyntheticEpisodeDataset(Dataset):
         self.env = type(env_name, (), {})()
         self.env.horizon = horizon
 
-    def __len__(self):
-        return self.data["measurement_self"].size(1)
-
-    def __getitem__(self, index):
-        d = self.data
-        img = d["imgs"][:, index]
-        depth = d["depths"][:, index] if self.use_depth else torch.empty(0, device=img.device)
-        x0bar = d["measurement_self"][:, index]
-        x0 = d["true_self"][:, index]
-        x1 = d["true_other"][:, index] if self.is_two_arm else torch.empty_like(x0)
-        obj = d["true_obj"][:, index] if self.obj_name is not None else torch.empty_like(x0)
-        return img, depth, x0bar, x0, x1, obj
-
     def refresh_data(self, num_episodes, camera_name=None, noise_scale=0.001):
         b = synthetic_batch((num_episodes, self.env.horizon), self.seed + self._refreshes, self.hw, self.use_depth, noise_scale, self.device)
         self._refreshes += 1
@@ -177,7 +184,7 @@ class SyntheticEpisodeDataset(Dataset):
         return img, depth, tm(d["measurement_self"]), tm(d["true_self"]), x1, obj
 
 
-class RecordedEpisodeDataset(Dataset):
+class RecordedEpisodeDataset(_TimestepItems):
     """MultiEpisodeDataset-shaped source of episodes RECORDED from the simulator elsewhere and read back from one `.npz` file: the
     keys of the reference's `MultiEpisodeDataset.data` (util/data_utils.py:85-92), raw instead of transformed --
 
@@ -197,7 +204,6 @@ class RecordedEpisodeDataset(Dataset):
     frame_dtype = torch.uint8
 
     def __init__(self, path, use_depth=False, obj_name=None, seed=1234):
-        import numpy as np
         with np.load(path, allow_pickle=False) as f:
             arrays = {k: f[k] for k in f.files}
         env_name = str(arrays.pop("env_name")) if "env_name" in arrays else "Recorded"
@@ -222,7 +228,6 @@ class RecordedEpisodeDataset(Dataset):
     @classmethod
     def _check(cls, arrays):
         """ValueError unless the arrays have the file format's ranks, dtypes and matching leading dimensions"""
-        import numpy as np
         unknown = set(arrays) - {"imgs", "depths"} - set(cls._POSES)
         if unknown:
             raise ValueError("unknown arrays {}: the file holds imgs, depths, true_self, true_other, true_obj, env_name".format(sorted(unknown)))
@@ -244,37 +249,29 @@ class RecordedEpisodeDataset(Dataset):
     def save(cls, path, env_name="Recorded", **arrays):
         """Write an episode file: imgs=, true_self= and optionally depths=, true_other=, true_obj= (numpy arrays or tensors), checked
         against the format above."""
-        import numpy as np
         arrays = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in arrays.items() if v is not None}
         cls._check(arrays)
         with open(path, "wb") as f:   # (np.savez would append ".npz" to a bare name)
             np.savez(f, env_name=np.array(str(env_name)), **arrays)
         return path
 
-    def __len__(self):
-        return self.data["measurement_self"].size(1)
-
-    def __getitem__(self, index):
-        d = self.data
-        img = d["imgs"][:, index]
-        depth = d["depths"][:, index] if self.use_depth else torch.empty(0)
-        x0bar = d["measurement_self"][:, index]
-        x0 = d["true_self"][:, index]
-        x1 = d["true_other"][:, index] if self.is_two_arm else torch.empty_like(x0)
-        obj = d["true_obj"][:, index] if self.obj_name is not None else torch.empty_like(x0)
-        return img, depth, x0bar, x0, x1, obj
-
-    def refresh_data(self, num_episodes, camera_name=None, noise_scale=0.001):
+    def _select(self, num_episodes):
+        """-> the numbers of the next `num_episodes` episodes in file order, wrapping around (also kept as the list `selected`)"""
         if num_episodes > self.num_recorded:
             raise ValueError("{} holds {} episodes; {} were asked for".format(self.path, self.num_recorded, num_episodes))
         sel = (torch.arange(num_episodes) + self._next) % self.num_recorded
         self._next = int(self._next + num_episodes) % self.num_recorded
         self.selected = sel.tolist()
+        return sel
+
+    def _measure(self, x0, noise_scale):
+        """a fresh measurement of the true poses x0, its noise drawn from the dataset's host generator"""
+        return noisy_measurement(x0, noise_scale, torch.randn(x0.shape, generator=self._gen))
+
+    def refresh_data(self, num_episodes, camera_name=None, noise_scale=0.001):
+        sel = self._select(num_episodes)
         data = {k: v[sel] for k, v in self.episodes.items()}
-        x0 = data["true_self"]
-        # measurement = truth + N(0, noise_scale I), the quaternion part renormalised (util/data_utils.py:162-167)
-        x0bar = x0 + (noise_scale ** 0.5) * torch.randn(x0.shape, generator=self._gen)
-        data["measurement_self"] = torch.cat([x0bar[..., :3], x0bar[..., 3:] / x0bar[..., 3:].norm(dim=-1, keepdim=True)], dim=-1)
+        data["measurement_self"] = self._measure(data["true_self"], noise_scale)
         self.data = data
 
 
@@ -317,14 +314,8 @@ class ResidentEpisodeDataset(RecordedEpisodeDataset):
         return self.env.horizon
 
     def refresh_data(self, num_episodes, camera_name=None, noise_scale=0.001):
-        if num_episodes > self.num_recorded:
-            raise ValueError("{} holds {} episodes; {} were asked for".format(self.path, self.num_recorded, num_episodes))
-        sel = (torch.arange(num_episodes) + self._next) % self.num_recorded
-        self._next = int(self._next + num_episodes) % self.num_recorded
-        self.selected = sel.tolist()
-        x0 = self._true_self_host[sel]
-        x0bar = x0 + (noise_scale ** 0.5) * torch.randn(x0.shape, generator=self._gen)
-        meas = torch.cat([x0bar[..., :3], x0bar[..., 3:] / x0bar[..., 3:].norm(dim=-1, keepdim=True)], dim=-1)
+        sel = self._select(num_episodes)
+        meas = self._measure(self._true_self_host[sel], noise_scale)
         sel_dev = sel.to(self.device)
         self.sel[:num_episodes].copy_(sel_dev.to(torch.int32))                      # in place: captured launches read these buffers
         self.pool["measurement_self"].index_copy_(0, sel_dev, meas.to(self.device))
@@ -368,7 +359,55 @@ class ResidentEpisodeDataset(RecordedEpisodeDataset):
         return WindowSampler(self, batch_size, sequence_length, stride, shuffle, seed)
 
 
-class WindowSampler:
+class _DeviceStepCounter:
+    """What WindowSampler, FrameAugment, DepthAugment and MeasurementNoise share: `seed`; a step counter that lives in device memory
+    once there is a device to keep it on (`_state`, an int32 tensor whose element 0 the launch itself advances) and on the host before
+    that (`_step0`); and the buffers a launch writes beside its output (`_kept`)."""
+
+    def __init__(self, seed):
+        self.seed = int(seed)
+        if not 0 <= self.seed < 2 ** 64:
+            raise ValueError("seed must fit 64 unsigned bits; got {!r}".format(seed))
+        self._state = None          # int32 device tensor, element 0 = the step counter
+        self._step0 = 0             # the counter while there is no device tensor yet
+        self._keep = {}
+
+    @staticmethod
+    def _wrap_i32(step):
+        """a 32-bit counter value as the int32 that holds the same bits"""
+        return step - (1 << 32) if step >= (1 << 31) else step
+
+    def _device_state(self, device):
+        if self._state is None or self._state.device != device:
+            self._state = torch.tensor([self._wrap_i32(self.step)], dtype=torch.int32, device=device)
+        return self._state
+
+    def _kept(self, key, make):
+        """the buffer(s) `make()` made for `key` the first time it was asked for.  Never freed or replaced while the object lives: a
+        captured call has their addresses, whatever shapes the object is called with afterwards."""
+        if key not in self._keep:
+            self._keep[key] = make()
+        return self._keep[key]
+
+    @property
+    def step(self):
+        """the step counter: the number of calls so far, replays of a captured call included (reads the device)"""
+        return self._step0 if self._state is None else int(self._state[0].item()) & 0xFFFFFFFF
+
+    def state_dict(self):
+        return {"seed": self.seed, "step": self.step}
+
+    def load_state_dict(self, sd):
+        seed, step = int(sd["seed"]), int(sd["step"])
+        if not (0 <= seed < 2 ** 64 and 0 <= step < 2 ** 32):
+            raise ValueError("{}.load_state_dict: seed / step out of range: {!r}".format(type(self).__name__, sd))
+        self.seed = seed
+        self._step0 = step
+        if self._state is not None:   # in place: a captured call keeps reading this tensor
+            self._state.fill_(self._wrap_i32(step))
+
+
+class WindowSampler(_DeviceStepCounter):
     """Shuffled minibatches of `batch_size` windows of `sequence_length` consecutive timesteps from a ResidentEpisodeDataset, drawn
     on the device (rpe_sample_windows + rpe_gather_rows; DESIGN.md "Minibatch sampling").  stride=None: window starts
     `sequence_length` apart -- the reference's chunk grid, in shuffled order; stride=1: every offset.  An epoch is the M = E K windows
@@ -389,9 +428,7 @@ class WindowSampler:
         self.batch_size, self.sequence_length = int(batch_size), int(sequence_length)
         self.stride = self.sequence_length if stride is None else int(stride)
         self.shuffle = bool(shuffle)
-        self.seed = int(seed)
-        if not 0 <= self.seed < 2 ** 64:
-            raise ValueError("seed must fit 64 unsigned bits; got {!r}".format(seed))
+        super().__init__(seed)
         if self.batch_size < 1:
             raise ValueError("batch_size must be at least 1; got {!r}".format(batch_size))
         self.num_episodes = dataset.num_selected
@@ -402,8 +439,7 @@ class WindowSampler:
         self.steps_per_epoch = self.num_windows // self.batch_size
         dev = dataset.device
         self.index = torch.zeros(1 + 2 * self.batch_size, dtype=torch.int32, device=dev)   # [0] the step used, then (episode, t0) per window
-        self._state = torch.zeros(1, dtype=torch.int32, device=dev)                         # element 0 = the step counter
-        self._out = None
+        self._state = torch.zeros(1, dtype=torch.int32, device=dev)                         # the counter: on the dataset's device at once
 
     def desc_fields(self):
         """the integers of rpe_sample_desc"""
@@ -412,12 +448,10 @@ class WindowSampler:
 
     def buffers(self):
         """the six-tuple of buffers every call writes and returns (made on first use and kept: a captured call has their addresses)"""
-        if self._out is None:
-            ds, s, n = self.dataset, self.sequence_length, self.batch_size
-            new = lambda k: torch.empty((s, n) + tuple(ds.pool[k].shape[2:]), dtype=ds.pool[k].dtype, device=ds.device)
-            self._out = (new("imgs"), new("depths") if ds.use_depth else None, new("measurement_self"), new("true_self"),
-                         new("true_other") if ds.is_two_arm else None, new("true_obj") if ds.obj_name is not None else None)
-        return self._out
+        ds, s, n = self.dataset, self.sequence_length, self.batch_size
+        new = lambda k: torch.empty((s, n) + tuple(ds.pool[k].shape[2:]), dtype=ds.pool[k].dtype, device=ds.device)
+        return self._kept("out", lambda: (new("imgs"), new("depths") if ds.use_depth else None, new("measurement_self"), new("true_self"),
+                                          new("true_other") if ds.is_two_arm else None, new("true_obj") if ds.obj_name is not None else None))
 
     def __call__(self):
         from .. import ops
@@ -426,21 +460,6 @@ class WindowSampler:
             raise ValueError("the sampler was made for {} selected episodes; refresh_data has selected {} since".format(self.num_episodes, ds.num_selected))
         ops.sample_windows(ops.sample_desc(**self.desc_fields()), ds.sel, self._state, out=self.index)
         return ds._batch(self.index, self.sequence_length, out=self.buffers())
-
-    @property
-    def step(self):
-        """the step counter: the number of calls so far, replays of a captured call included (reads the device)"""
-        return int(self._state[0].item()) & 0xFFFFFFFF
-
-    def state_dict(self):
-        return {"seed": self.seed, "step": self.step}
-
-    def load_state_dict(self, sd):
-        seed, step = int(sd["seed"]), int(sd["step"])
-        if not (0 <= seed < 2 ** 64 and 0 <= step < 2 ** 32):
-            raise ValueError("WindowSampler.load_state_dict: seed / step out of range: {!r}".format(sd))
-        self.seed = seed
-        self._state.fill_(step - (1 << 32) if step >= (1 << 31) else step)   # in place: a captured call keeps reading this tensor
 
 
 NOISE_SUM_STD = 147.8005   # standard deviation of the sum of four uniform bytes: sqrt(4 (256^2 - 1) / 12)
@@ -457,34 +476,6 @@ def _jitter_range(name, amount):
     if not 0.0 <= a <= 3.0:
         raise ValueError("{} must lie in [0, 3] (factors up to 4); got {!r}".format(name, amount))
     return _q16(max(0.0, 1.0 - a)), _q16(1.0 + a)
-
-
-class _DeviceStepCounter:
-    """What FrameAugment, DepthAugment and MeasurementNoise share: `seed`, and a step counter that lives in device memory once the
-    object has run (`_state`, an int32 tensor whose element 0 the launch itself advances) and on the host before that (`_step0`)."""
-
-    def _device_state(self, device):
-        if self._state is None or self._state.device != device:
-            step = self.step
-            self._state = torch.tensor([step - (1 << 32) if step >= (1 << 31) else step], dtype=torch.int32, device=device)
-        return self._state
-
-    @property
-    def step(self):
-        """the step counter: the number of calls so far, replays of a captured call included (reads the device)"""
-        return self._step0 if self._state is None else int(self._state[0].item()) & 0xFFFFFFFF
-
-    def state_dict(self):
-        return {"seed": self.seed, "step": self.step}
-
-    def load_state_dict(self, sd):
-        seed, step = int(sd["seed"]), int(sd["step"])
-        if not (0 <= seed < 2 ** 64 and 0 <= step < 2 ** 32):
-            raise ValueError("{}.load_state_dict: seed / step out of range: {!r}".format(type(self).__name__, sd))
-        self.seed = seed
-        self._step0 = step
-        if self._state is not None:   # in place: a captured call keeps reading this tensor
-            self._state.fill_(step - (1 << 32) if step >= (1 << 31) else step)
 
 
 class FrameAugment(_DeviceStepCounter):
@@ -532,14 +523,9 @@ class FrameAugment(_DeviceStepCounter):
                 raise ValueError('erase_fill is "mean", "noise" or an (r, g, b) tuple of bytes; got {!r}'.format(erase_fill))
             self.fill_mode, self.fill_rgb = 0, rgb
         self.per_episode = bool(per_episode)
-        self.seed = int(seed)
-        if not 0 <= self.seed < 2 ** 64:
-            raise ValueError("seed must fit 64 unsigned bits; got {!r}".format(seed))
+        super().__init__(seed)
         self.last_params = None     # device table of the last call: [0] the step used, then per stream qb qc qs erase top left h w
         self.last_geometry = None   # (Hs, Ws, frames, group) of the last call
-        self._state = None          # int32 device tensor, element 0 = the step counter
-        self._step0 = 0             # the counter while there is no device tensor yet
-        self._buffers = {}
 
     def erase_bounds(self, size):
         """erase_scale as pixel bounds (lo, hi) of a side of `size` pixels, 1 <= lo <= hi <= size"""
@@ -570,11 +556,8 @@ class FrameAugment(_DeviceStepCounter):
         group = frames.shape[1] if self.per_episode and frames.dim() == 5 else 0
         b = frames.numel() // (hs * ws * 3)
         state = self._device_state(frames.device)
-        key = (b, group, frames.device)
-        if key not in self._buffers:   # kept: a captured call has their addresses
-            self._buffers[key] = (torch.empty(1 + 8 * (group or b), dtype=torch.int32, device=frames.device),
-                                  torch.empty(b, dtype=torch.int64, device=frames.device))
-        params, sums = self._buffers[key]
+        params, sums = self._kept((b, group, frames.device), lambda: (torch.empty(1 + 8 * (group or b), dtype=torch.int32, device=frames.device),
+                                                                      torch.empty(b, dtype=torch.int64, device=frames.device)))
         out = ops.augment_frames_u8(frames, ops.augment_desc(**self.desc_fields(hs, ws, group)), state, out=out, params=params, sums=sums)
         self.last_params = params
         self.last_geometry = (int(hs), int(ws), int(b), int(group))   # what DepthAugment(share_erase=self) checks its own batch against
@@ -647,16 +630,11 @@ class DepthAugment(_DeviceStepCounter):
             self.clamp = (lo, hi)
         self.hole_value, self.occluder_value = float(hole_value), float(occluder_value)
         self.per_frame = bool(per_frame)
-        self.seed = int(seed)
-        if not 0 <= self.seed < 2 ** 64:
-            raise ValueError("seed must fit 64 unsigned bits; got {!r}".format(seed))
+        super().__init__(seed)
         if share_erase is not None and not isinstance(share_erase, FrameAugment):
             raise ValueError("share_erase takes the FrameAugment of the RGB frames; got {!r}".format(type(share_erase).__name__))
         self.share_erase = share_erase
         self.last_params = None     # device table of the last call: [0] the step used, then per stream count and 4 x (top, left, h, w)
-        self._state = None          # int32 device tensor, element 0 = the step counter
-        self._step0 = 0             # the counter while there is no device tensor yet
-        self._buffers = {}
 
     def hole_bounds(self, size):
         """hole_scale as pixel bounds (lo, hi) of a side of `size` pixels, 1 <= lo <= hi <= size"""
@@ -710,10 +688,7 @@ class DepthAugment(_DeviceStepCounter):
         b = depth.numel() // (hs * ws)
         rgb_params, rgb_group = self.shared_table(hs, ws, b, group)
         state = self._device_state(depth.device)
-        key = (b, group, depth.device)
-        if key not in self._buffers:   # kept: a captured call has its address
-            self._buffers[key] = torch.empty(1 + ops.DEPTH_AUGMENT_ROW * (group or b), dtype=torch.int32, device=depth.device)
-        params = self._buffers[key]
+        params = self._kept((b, group, depth.device), lambda: torch.empty(1 + ops.DEPTH_AUGMENT_ROW * (group or b), dtype=torch.int32, device=depth.device))
         out = ops.augment_depth_f32(depth, ops.depth_augment_desc(**self.desc_fields(hs, ws, group)), state, out=out, params=params,
                                     rgb_params=rgb_params, rgb_group=rgb_group)
         self.last_params = params
@@ -740,13 +715,8 @@ class MeasurementNoise(_DeviceStepCounter):
         self.correlation = float(correlation)
         if not 0.0 <= self.correlation < 1.0:
             raise ValueError("correlation must lie in [0, 1); got {!r}".format(correlation))
-        self.seed = int(seed)
-        if not 0 <= self.seed < 2 ** 64:
-            raise ValueError("seed must fit 64 unsigned bits; got {!r}".format(seed))
+        super().__init__(seed)
         self.last_picks = None      # device table of the last call: [0] the step used, then each lane's scale index
-        self._state = None          # int32 device tensor, element 0 = the step counter
-        self._step0 = 0             # the counter while there is no device tensor yet
-        self._picks = None
 
     @staticmethod
     def check_poses(x0):
@@ -771,11 +741,104 @@ class MeasurementNoise(_DeviceStepCounter):
             raise ValueError("MeasurementNoise: out must be a contiguous fp32 tensor of x0's shape on its device")
         desc = ops.measure_desc(**self.desc_fields(s, n))
         state = self._device_state(x0.device)
-        if self._picks is None or self._picks.numel() != 1 + n or self._picks.device != x0.device:   # kept: a captured call has its address
-            self._picks = torch.zeros(1 + n, dtype=torch.int32, device=x0.device)
-        out = ops.measurement_noise(x0, desc, state, picks=self._picks, out=out)
-        self.last_picks = self._picks
+        picks = self._kept((n, x0.device), lambda: torch.zeros(1 + n, dtype=torch.int32, device=x0.device))
+        out = ops.measurement_noise(x0, desc, state, picks=picks, out=out)
+        self.last_picks = picks
         return out
+
+
+def model_batch(batch, requires_sequence):
+    """A time-major six-tuple (S, N, ...) as the model takes it: a model without a sequence walks S = 1 and takes the tensors without
+    that dimension (the reference squeezes the leading batch-of-1 dim, util/learn_utils.py:141-149 there).  Views: the addresses stay."""
+    return tuple(batch) if requires_sequence else tuple(None if t is None else t[0] for t in batch)
+
+
+class TrainInputs:
+    """The device stages between a dataset and the model in a train step, all optional, as ONE object that train() and GraphedTrainStep
+    both build and call ("Input stages").  They run in one fixed order on the six-tuple
+    (img, depth, x0bar, x0, x1, obj):
+
+        sampler            draws the batch itself (its own buffers)
+        measurement_noise  reads x0 (field 3), its result replaces x0bar (field 2)
+        augment            reads the raw frames (field 0), its result replaces them
+        depth_augment      reads the raw depth (field 1), its result replaces it
+
+    The one constraint on the order: depth_augment comes after augment, because a DepthAugment(share_erase=augment) reads the table
+    the RGB augmentation of the same step wrote.  Everything else is free -- each stage has a counter of its own and writes a tensor
+    of its own -- and the remaining fields pass through as they are.  The stages are validated here, once, against the model and the
+    dataset (only `use_depth`, and with a sampler `requires_sequence` / `sequence_length`, are read of the model)."""
+
+    def __init__(self, model, dataset=None, sampler=None, measurement_noise=None, augment=None, depth_augment=None):
+        if measurement_noise is not None and not isinstance(measurement_noise, MeasurementNoise):
+            raise ValueError("measurement_noise=... takes a util.data_utils.MeasurementNoise; got {!r}".format(type(measurement_noise).__name__))
+        if depth_augment is not None:
+            if not isinstance(depth_augment, DepthAugment):
+                raise ValueError("depth_augment=... takes a util.data_utils.DepthAugment; got {!r}".format(type(depth_augment).__name__))
+            if not getattr(model, "use_depth", False):
+                raise ValueError("depth_augment=... needs a model built with use_depth; {} does not read depth".format(type(model).__name__))
+            if depth_augment.share_erase is not None and depth_augment.share_erase is not augment:
+                raise ValueError("depth_augment.share_erase must be the FrameAugment given as augment=... to the same call: the occluder is shared "
+                                 "with the RGB frames of the same step")
+        if augment is not None and getattr(dataset, "frame_dtype", torch.uint8) != torch.uint8:
+            raise ValueError("augment=... needs raw uint8 frames (RecordedEpisodeDataset); {} hands out {} images".format(
+                type(dataset).__name__, dataset.frame_dtype))
+        self.model, self.sampler = model, None
+        self.measurement_noise, self.augment, self.depth_augment = measurement_noise, augment, depth_augment
+        if sampler is not None:
+            self.draw_from(sampler)
+
+    def draw_from(self, sampler):
+        """make `sampler` (a WindowSampler) the source of the batches (train() has none before its first refresh)"""
+        want = self.model.sequence_length if self.model.requires_sequence else 1
+        if sampler.sequence_length != want:
+            raise ValueError("the model takes windows of {} timesteps; the sampler draws {}".format(want, sampler.sequence_length))
+        self.sampler = sampler
+
+    @property
+    def _passes(self):
+        return self.measurement_noise is None and self.augment is None and self.depth_augment is None
+
+    @staticmethod
+    def _depth(batch):
+        if batch[1] is None:
+            raise ValueError("depth_augment=... needs a batch with depth frames; this one has none")
+        return batch[1]
+
+    def fed_like(self, static):
+        """-> the six-tuple a captured step feeds the model for the fixed inputs `static`: `static` with a new buffer in every slot a
+        stage writes (`static` itself without one), after the stages' own checks of what they will read"""
+        if self._passes:
+            return static
+        fed = list(static)
+        if self.augment is not None:
+            self.augment.check_frames(static[0])
+            fed[0] = torch.empty_like(static[0])
+        if self.measurement_noise is not None:
+            self.measurement_noise.check_poses(static[3])
+            fed[2] = torch.empty_like(static[3])
+        if self.depth_augment is not None:
+            self.depth_augment.check_depth(self._depth(static))
+            fed[1] = torch.empty_like(static[1])
+        return tuple(fed)
+
+    def __call__(self, batch=None, out=None):
+        """-> what the model is fed for `batch`.  With a sampler the batch is drawn here: pass None, or -- the captured step -- the
+        views of the sampler's buffers that are to be read.  out: a six-tuple (`fed_like`) whose slots the stages write; without it
+        every stage returns a new tensor and the batch's own are not written."""
+        if self.sampler is not None:
+            drawn = self.sampler()
+            if batch is None:
+                batch = model_batch(drawn, self.model.requires_sequence)
+        if self._passes:
+            return batch
+        fed, out = list(batch), out or (None,) * 6
+        if self.measurement_noise is not None:
+            fed[2] = self.measurement_noise(batch[3].contiguous(), out=out[2])
+        if self.augment is not None:
+            fed[0] = self.augment(batch[0], out=out[0])
+        if self.depth_augment is not None:   # after `augment`: the RGB table of this step exists
+            fed[1] = self.depth_augment(self._depth(batch).contiguous(), out=out[1])
+        return tuple(fed)
 
 
 
@@ -799,6 +862,7 @@ class FramePrefetcher:
         self._dev = [None] * self.depth      # per slot: list of device buffers
         self._ready = [None] * self.depth    # per slot: copy-finished event
         self._free = [None] * self.depth     # per slot: consumer-finished event (the slot may be overwritten after it)
+        self._src_keep = [None] * self.depth   # per slot: the host tensors its last copy read
 
     def _stage(self, slot, batch):
         items = list(batch) if isinstance(batch, (tuple, list)) else [batch]
@@ -822,7 +886,6 @@ class FramePrefetcher:
             else:
                 p.copy_(t)                                  # host memcpy into the pinned buffer (on the caller's thread: keep
                 src.append(p)                               # loaders pinning, or this copy is what the GPU waits for)
-        self._src_keep = getattr(self, "_src_keep", [None] * self.depth)
         self._src_keep[slot] = src                          # sources stay alive until the slot is staged again
         with torch.cuda.stream(self.stream):
             for d, p in zip(self._dev[slot], src):

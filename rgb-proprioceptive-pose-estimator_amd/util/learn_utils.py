@@ -25,6 +25,7 @@ import torch
 import torch.distributed as dist
 
 from ..dist import GradSync, broadcast_parameters, shard_bounds
+from .data_utils import FramePrefetcher, TrainInputs, model_batch, noisy_measurement, window_counts
 
 
 def _writer(logging):
@@ -59,7 +60,6 @@ def _chunks(dataset, horizon, seq, use_depth):
         for t0 in range(0, horizon, seq):
             yield dataset.chunk(t0, min(seq, horizon - t0))
         return
-    from .data_utils import FramePrefetcher
     first = dataset[0][0]
     if torch.as_tensor(first).is_cuda:   # device-resident tensors behind a plain __getitem__: just stack
         yield from _host_chunks(dataset, horizon, seq, use_depth)
@@ -71,7 +71,6 @@ def sampled_steps_per_epoch(num_episodes, world, horizon, sequence_length, strid
     """optimizer steps of one sampled `train` phase (train(batch_size=...)): every rank draws from its own shard of the episodes
     (dist.shard_bounds), and all take the step count of the SMALLEST shard -- its windows // batch_size -- so the collectives stay
     matched.  A function of the arguments alone: every rank computes the same number without communication."""
-    from .data_utils import window_counts
     steps = []
     for r in range(int(world)):
         lo, hi = shard_bounds(num_episodes, r, world)
@@ -138,56 +137,21 @@ class GraphedTrainStep:
         if not getattr(optimizer, "capturable", False):
             raise RuntimeError("GraphedTrainStep needs FusedAdam(..., capturable=True): the step count must live on the device")
         self.model, self.criterion, self.optimizer, self.train_obj_pose = model, criterion, optimizer, train_obj_pose
-        # sampler (util.data_utils.WindowSampler): the captured step BEGINS with the sampler's two launches, which write the sampler's
-        # own buffers -- these are the static inputs, `example_batch` may be None and __call__ takes no batch.  The sampler's step
-        # counter lives on the device, so every replay trains on the next batch of the stream (the warm-up steps advance it too).
-        self.sampler = sampler
-        if sampler is not None:
-            want = model.sequence_length if model.requires_sequence else 1
-            if sampler.sequence_length != want:
-                raise ValueError("the model takes windows of {} timesteps; the sampler draws {}".format(want, sampler.sequence_length))
-            example_batch = sampler.buffers()   # (no launch: the counter stays; the views below keep the buffers' addresses)
-            if not model.requires_sequence:
-                example_batch = tuple(None if t is None else t[0] for t in example_batch)
-            self.static = tuple(example_batch)
+        # The input stages (util.data_utils.TrainInputs) are part of the captured step, in front of the model: they read the static
+        # inputs and write buffers of their own, `fed`, which is what the model is given.  Their step counters live on the device and
+        # the captured launches advance them, so every replay draws afresh (the warm-up steps advance them too, the capture does not).
+        # With a sampler the step BEGINS with its two launches, which write the sampler's own buffers: these are the static inputs,
+        # `example_batch` may be None and __call__ takes no batch.
+        inputs = TrainInputs(model, sampler=sampler, measurement_noise=measurement_noise, augment=augment, depth_augment=depth_augment)
+        self.sampler, self.measurement_noise, self.augment, self.depth_augment = sampler, measurement_noise, augment, depth_augment
+        if sampler is not None:   # (buffers(): no launch, the counter stays; views keep the buffers' addresses)
+            self.static = model_batch(sampler.buffers(), model.requires_sequence)
         else:
             self.static = tuple(None if t is None else t.clone() for t in example_batch)
-        # augment (util.data_utils.FrameAugment): the augmentation is part of the captured step -- it reads the static raw frames and
-        # writes a buffer of its own, which is what the model is fed.  Its step counter lives on the device and the captured launch
-        # advances it, so every replay draws fresh parameters (the warm-up steps below advance it as well).
-        self.augment = augment
-        self.fed = self.static
-        if augment is not None:
-            augment.check_frames(self.static[0])
-            self.fed = (torch.empty_like(self.static[0]),) + self.static[1:]
-        # measurement_noise (util.data_utils.MeasurementNoise): the draw is part of the captured step, after the sampler's launches -- it
-        # reads the static true poses x0 and writes a buffer of its own, which takes the place of x0bar in what the model is fed.  Its
-        # step counter lives on the device: every replay draws fresh noise (the warm-up steps advance it, the capture does not).
-        self.measurement_noise = measurement_noise
-        if measurement_noise is not None:
-            measurement_noise.check_poses(self.static[3])
-            self.fed = self.fed[:2] + (torch.empty_like(self.static[3]),) + self.fed[3:]
-        # depth_augment (util.data_utils.DepthAugment): inside the captured step as well, AFTER `augment`, so that the RGB table of the
-        # same step exists where the two share the occluder -- it reads the static raw depth and writes a buffer of its own, which takes
-        # the place of fed[1].  Its counter lives on the device and advances with every replay (and with the warm-up steps).
-        self.depth_augment = depth_augment
-        if depth_augment is not None:
-            _check_depth_augment(depth_augment, model, augment)
-            if self.static[1] is None:
-                raise ValueError("GraphedTrainStep(depth_augment=...) needs a batch with depth frames")
-            depth_augment.check_depth(self.static[1])
-            self.fed = self.fed[:1] + (torch.empty_like(self.static[1]),) + self.fed[2:]
+        self.fed = inputs.fed_like(self.static)
 
         def step():
-            if sampler is not None:
-                sampler()
-            if measurement_noise is not None:
-                measurement_noise(self.static[3], out=self.fed[2])
-            if augment is not None:
-                augment(self.static[0], out=self.fed[0])
-            if depth_augment is not None:
-                depth_augment(self.static[1], out=self.fed[1])
-            return train_step(model, self.fed, criterion, optimizer, train_obj_pose, "train", None)
+            return train_step(model, inputs(self.static, out=self.fed), criterion, optimizer, train_obj_pose, "train", None)
 
         model.train()
         side = torch.cuda.Stream()
@@ -292,11 +256,7 @@ def sweep_measurements(x0, noise_scales, z):
     """x0 (..., 7) true poses, z a standard-normal draw of that shape -> (K, ..., 7): x0 + sqrt(s_k) z with the quaternion part
     renormalised, as RecordedEpisodeDataset.refresh_data makes a measurement (util/data_utils.py:162-167 of the reference).  The ONE
     draw serves every scale, so the scales differ in nothing but the scale; s = 0 gives the true pose back."""
-    out = []
-    for s in noise_scales:
-        xb = x0 + (float(s) ** 0.5) * z
-        out.append(torch.cat([xb[..., :3], xb[..., 3:] / xb[..., 3:].norm(dim=-1, keepdim=True)], dim=-1))
-    return torch.stack(out, 0)
+    return torch.stack([noisy_measurement(x0, float(s), z) for s in noise_scales], 0)
 
 
 def sweep_draw(num_episodes, horizon, noise_seed):
@@ -628,18 +588,6 @@ def telemetry_report(optimizer, model, host=None):
     return report
 
 
-def _check_depth_augment(depth_augment, model, augment):
-    """ValueError unless `depth_augment` is a DepthAugment that this model and this call's `augment` can honour"""
-    from .data_utils import DepthAugment
-    if not isinstance(depth_augment, DepthAugment):
-        raise ValueError("depth_augment=... takes a util.data_utils.DepthAugment; got {!r}".format(type(depth_augment).__name__))
-    if not getattr(model, "use_depth", False):
-        raise ValueError("depth_augment=... needs a model built with use_depth; {} does not read depth".format(type(model).__name__))
-    if depth_augment.share_erase is not None and depth_augment.share_erase is not augment:
-        raise ValueError("depth_augment.share_erase must be the FrameAugment given as augment=... to the same call: the occluder is shared "
-                         "with the RGB frames of the same step")
-
-
 def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_per_epoch, num_val_episodes_per_epoch, params, device,
           save_path='default', save_model=True, logging=True, *, save_optimizer=False, augment=None, batch_size=None, window_stride=None,
           shuffle_seed=0, measurement_noise=None, telemetry=None, telemetry_log=None, depth_augment=None):
@@ -662,10 +610,10 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
     measurement_noise (util.data_utils.MeasurementNoise): in the `train` phase the model is fed measurement_noise(x0), drawn on the
     device afresh at every step, in place of the dataset's x0bar (drawn on the host once per refresh); it needs the batch's x0 rows
     only, so every dataset takes it.  The `val` phase keeps the dataset's measurements, and the dataset's own pool is not written.
-    depth_augment (util.data_utils.DepthAugment): applied on the device to the depth frames of the `train` phase, AFTER `augment`, so
-    that the RGB table of the same step exists where the two share the occluder; the `val` phase sees the recorded depth and the
-    dataset's own depth is not written.  A ValueError for a model without use_depth, or when its share_erase names a FrameAugment
-    that is not the `augment` of this call.
+    depth_augment (util.data_utils.DepthAugment): applied on the device to the depth frames of the `train` phase; the `val` phase sees
+    the recorded depth and the dataset's own depth is not written.  A ValueError for a model without use_depth, or when its
+    share_erase names a FrameAugment that is not the `augment` of this call.
+    These stages and the sampler run as one util.data_utils.TrainInputs, which validates them and fixes their order.
     telemetry (None or K >= 1; needs FusedAdam(telemetry=K) with the same K): at the end of every `train` phase the optimizer's
     per-tensor table of the last measured step is read WITH the phase's one host read (no synchronisation per step is added) and
     written as Telemetry/grad_norm/<name>, Telemetry/update_ratio/<name>, Telemetry/zero_frac/<name>; when a tensor has seen
@@ -676,20 +624,13 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
             telemetry, telemetry, type(optimizer).__name__, getattr(optimizer, "telemetry", None)))
     if telemetry is None and telemetry_log is not None:
         raise ValueError("train(telemetry_log=...) belongs to telemetry=K")
-    if measurement_noise is not None:
-        from .data_utils import MeasurementNoise
-        if not isinstance(measurement_noise, MeasurementNoise):
-            raise ValueError("train(measurement_noise=...) takes a util.data_utils.MeasurementNoise; got {!r}".format(type(measurement_noise).__name__))
-    if depth_augment is not None:
-        _check_depth_augment(depth_augment, model, augment)
+    # the device stages of the `train` phase, validated here: before the model, the optimizer or the device are touched
+    inputs = TrainInputs(model, dataset, measurement_noise=measurement_noise, augment=augment, depth_augment=depth_augment)
     if batch_size is not None and not hasattr(dataset, "sampler"):
         raise ValueError("train(batch_size=...) draws minibatches on the device and needs a dataset with sampler() (ResidentEpisodeDataset); "
                          "{} has none".format(type(dataset).__name__))
     if batch_size is None and (window_stride is not None or shuffle_seed != 0):
         raise ValueError("train(window_stride=..., shuffle_seed=...) belong to batch_size=...; without it the episodes are walked in lockstep")
-    if augment is not None and getattr(dataset, "frame_dtype", torch.uint8) != torch.uint8:
-        raise ValueError("train(augment=...) needs raw uint8 frames (RecordedEpisodeDataset); {} hands out {} images".format(
-            type(dataset).__name__, dataset.frame_dtype))
     train_obj_pose = hasattr(model, "object_name")
     dt_string = datetime.now().strftime("%d-%m-%Y_%H-%M-%S")
     since = time.time()
@@ -711,7 +652,6 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
         broadcast_parameters(model._arena.flat, list(model.buffers()))
         grad_sync = GradSync(model._arena.grad).attach(model)
     seq = model.sequence_length if model.requires_sequence else 1
-    sampler = None   # made after the first `train` refresh: it reads the number of selected episodes
     fname = "{}_{}_{}hzn_{}ep_{}.pth".format(type(model).__name__, type(dataset.env).__name__, dataset.env.horizon,
                                              num_epochs * num_train_episodes_per_epoch, dt_string)
     if save_model and rank == 0:
@@ -733,33 +673,20 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
             ema_sd = None
             sampled = batch_size is not None and phase == "train"
             if sampled:
-                if sampler is None:
-                    sampler = dataset.sampler(batch_size, sequence_length=seq, stride=window_stride, shuffle=True, seed=shuffle_seed + rank)
-                steps = sampled_steps_per_epoch(num_episodes, world, horizon, seq, sampler.stride, batch_size)
+                if inputs.sampler is None:   # made after the first `train` refresh: it reads the number of selected episodes
+                    inputs.draw_from(dataset.sampler(batch_size, sequence_length=seq, stride=window_stride, shuffle=True, seed=shuffle_seed + rank))
+                steps = sampled_steps_per_epoch(num_episodes, world, horizon, seq, inputs.sampler.stride, batch_size)
                 if steps < 1:
                     raise ValueError("the smallest shard of {} episodes over {} ranks has fewer than batch_size = {} windows".format(num_episodes, world, batch_size))
                 model.reset_initial_state(batch_size)
-                batches = (sampler() for _ in range(steps))
+                batches = (None for _ in range(steps))   # `inputs` draws them
             else:
-                batches = _chunks(dataset, horizon, seq, model.use_depth if hasattr(model, "use_depth") else False)
+                batches = (model_batch(b, model.requires_sequence) for b in _chunks(dataset, horizon, seq, getattr(model, "use_depth", False)))
             with optimizer.averaged_weights(model) if phase == "val" and has_ema else contextlib.nullcontext():   # validate the average
-                for img, depth, x0bar, x0, x1, obj in batches:
-                    if not model.requires_sequence:  # the reference squeezes the leading batch-of-1 dim (learn_utils.py:141-149)
-                        img, x0bar, x0 = img[0], x0bar[0], x0[0]
-                        depth = None if depth is None else depth[0]
-                        x1 = None if x1 is None else x1[0]
-                        obj = None if obj is None else obj[0]
-                    if augment is not None and phase == "train":
-                        if img.dtype != torch.uint8:
-                            raise ValueError("train(augment=...) needs raw uint8 frames; the dataset hands out {} images".format(img.dtype))
-                        img = augment(img)
-                    if depth_augment is not None and phase == "train":   # after `augment`: the RGB table of this step exists
-                        if depth is None:
-                            raise ValueError("train(depth_augment=...): the dataset hands out no depth frames")
-                        depth = depth_augment(depth.contiguous())   # a new tensor: the dataset's own depth is not written
-                    if measurement_noise is not None and phase == "train":
-                        x0bar = measurement_noise(x0.contiguous())
-                    loss, pe, oe = train_step(model, (img, depth, x0bar, x0, x1, obj), criterion, optimizer, train_obj_pose, phase, grad_sync)
+                for batch in batches:
+                    if phase == "train":   # new tensors: what the dataset handed out is not written
+                        batch = inputs(batch)
+                    loss, pe, oe = train_step(model, batch, criterion, optimizer, train_obj_pose, phase, grad_sync)
                     sums += torch.stack([loss.double(), pe.double(), oe.double()])
                     if clip_sums is not None:
                         clip_sums += torch.stack([optimizer.grad_norm.double(), (optimizer.clip_coef < 1.0).double()])

@@ -254,6 +254,63 @@ def test_captured_sampler_draws_the_next_batch_at_every_replay(tmp_path):
     _check_batch(batch, res, want, 3)
 
 
+# -- the input pipeline -----------------------------------------------------------------------------------------------------------
+
+def test_the_four_stages_together_equal_their_oracles(tmp_path):
+    """TrainInputs, eager (nothing is captured): sampler, measurement noise, frame and depth augmentation in one call, each against its
+    own numpy oracle at steps 0, 1, 2.  A namespace stands in for the model: no trunk runs."""
+    import types
+    import _augment_oracle as ao
+    import _depth_augment_oracle as do
+    import _measure_oracle as mo
+    from test_gpu_augment import _desc_of as rgb_desc
+    from test_gpu_depth_augment import _bits, _desc_of as depth_desc, _episode_arrays
+    from rgb_proprioceptive_pose_estimator_amd.util.data_utils import (DepthAugment, FrameAugment, MeasurementNoise, RecordedEpisodeDataset,
+                                                                       ResidentEpisodeDataset, TrainInputs)
+    path = RecordedEpisodeDataset.save(str(tmp_path / "episodes.npz"), env_name="Lift", **_episode_arrays(e=4, t=4, hw=64))
+    ds = ResidentEpisodeDataset(path, use_depth=True, obj_name="cube")
+    ds.refresh_data(3)
+    before = {k: v.clone() for k, v in ds.pool.items()}
+    host = {k: v.cpu().numpy() for k, v in before.items()}
+    sampler = ds.sampler(4, seed=6)
+    noise = MeasurementNoise([0.001, 0.01], correlation=0.5, seed=3)
+    aug = FrameAugment(brightness=0.3, erase_prob=1.0, seed=8)
+    daug = DepthAugment(noise=(0.01, 0.01), holes=(1, 2), share_erase=aug, occluder_value=0.25, seed=8)
+    model = types.SimpleNamespace(use_depth=True, requires_sequence=False, sequence_length=1)
+    inputs = TrainInputs(model, ds, sampler=sampler, measurement_noise=noise, augment=aug, depth_augment=daug)
+    stages = (sampler, noise, aug, daug)
+    assert [s.step for s in stages] == [0, 0, 0, 0]
+    for k in range(3):
+        img, depth, x0bar, x0, x1, obj = inputs()
+        index = so.window_index(sampler.desc_fields(), ds.selected, k)
+        assert np.array_equal(sampler.index.cpu().numpy(), index), k
+        raw = {key: so.gather(host[key], index, 1)[0] for key in ("imgs", "depths", "true_self", "true_obj")}      # S = 1, squeezed away
+        want_img, table, _ = ao.augment(raw["imgs"], rgb_desc(aug, 64, 64, 0), k)
+        assert img.dtype == torch.uint8 and np.array_equal(img.cpu().numpy(), want_img), k
+        assert np.array_equal(aug.last_params.cpu().numpy(), table) and table[1:].reshape(-1, 8)[:, 3].all()      # every frame has an occluder
+        want_depth, want_params = do.augment(raw["depths"], depth_desc(daug, 64, 64, 0), k, rgb_params=table)
+        assert np.array_equal(_bits(depth.cpu().numpy()), _bits(want_depth)), k
+        assert np.array_equal(daug.last_params.cpu().numpy(), want_params) and (depth == 0.25).any().item()         # the shared occluder is in it
+        want_meas, want_picks = mo.measure(raw["true_self"], 3, [0.001, 0.01], 0.5, k)
+        beyond, differ = mo.compare(x0bar.cpu().numpy(), want_meas)
+        print("step %d: x0bar %d of %d elements beyond one ulp, %d differ" % (k, beyond, want_meas.size, differ))
+        assert beyond == 0 and np.array_equal(noise.last_picks.cpu().numpy(), want_picks), k
+        # the fields no stage writes are the sampler's own
+        assert np.array_equal(x0.cpu().numpy(), raw["true_self"]) and np.array_equal(obj.cpu().numpy(), raw["true_obj"]) and x1 is None
+        assert [s.step for s in stages] == [k + 1] * 4
+    for key, v in before.items():      # nothing wrote the dataset's pools
+        assert torch.equal(ds.pool[key].view(torch.uint8), v.view(torch.uint8)), key
+    # the picks of one batch size outlive a call at another: a captured call would still be writing them
+    x8 = torch.from_numpy(host["true_self"][:2].reshape(8, 7)).cuda()
+    noise(x8)
+    first, ptr = noise.last_picks, noise.last_picks.data_ptr()
+    noise(x8[:4].contiguous())
+    assert noise.last_picks.numel() == 5 and noise.last_picks.data_ptr() != ptr
+    assert first.numel() == 9 and first.data_ptr() == ptr and noise._kept((8, x8.device), None) is first
+    noise(x8)
+    assert noise.last_picks is first and noise.step == 6
+
+
 # -- through the training loop ----------------------------------------------------------------------------------------------------
 
 def _model(seed=3):
