@@ -301,6 +301,17 @@ typedef struct {
  * one, so a captured call draws the next batch at every replay.  index: device, 1 + 2 N ints, receives [0] = the step used, then per
  * window (episode number in the file, first timestep).  E K must stay below 2^31.  One launch of one workgroup. */
 int rpe_sample_windows(const rpe_sample_desc* d, const int* sel, unsigned* state, int* index, void* stream);
+/* Episodes of unequal length: the same draw when episode e of the selection has only len_e = clamp(lengths[sel[e]], 0, T) of its T
+ * rows (the rest is padding).  lengths: device, one entry per episode IN THE FILE, read as lengths[sel[e]] at every launch -- like sel,
+ * so a captured call follows a refresh.  K_e = len_e >= S ? (len_e - S) / stride + 1 : 0, P_0 = 0, P_{e+1} = P_e + K_e, M = P_E: the
+ * window table is scanned on the device (LDS), M and the half width of the Feistel domain, (max(bitlen(M - 1), 2) + 1) / 2, belong to
+ * the launch.  g, epoch, pos, the bijection, its key, purpose word and cycle walk are rpe_sample_windows'; window w lies in episode e =
+ * the largest index with P_e <= w (binary search) and starts at (w - P_e) stride, so t0 + S <= len_e: index[1 + 2 i] = sel[e],
+ * index[2 + 2 i] = (w - P_e) stride.  index[0] and the counter as above.  With all lengths equal the table is rpe_sample_windows' bit
+ * for bit.  M == 0 (no episode holds a window): every window is (sel[0], 0), in bounds for the gather and meaningless.
+ * E <= 8192 (RPE_ERR_SHAPE beyond: the prefix table is 32 KB of LDS); E ((T - S) / stride + 1) must stay below 2^31.  One launch of
+ * one workgroup. */
+int rpe_sample_windows_ragged(const rpe_sample_desc* d, const int* sel, const int* lengths, unsigned* state, int* index, void* stream);
 /* out row s N + n <- pool row index.episode[n] * T + index.t0[n] + s for s < S, n < N; rows of row_bytes bytes, 64-bit offsets.  pool:
  * device, [episodes in the file][T] rows; out: device, [S][N] rows, not overlapping the pool; index: as rpe_sample_windows writes it
  * (the entries are trusted: episode < episodes in the file, t0 + S <= T).  16-byte loads and stores when row_bytes and both pointers
@@ -639,6 +650,14 @@ int rpe_lstm_cell_bwd(const float* gates_act, const float* c_prev, const float* 
 int rpe_pose_loss(const float* pred, const float* truth, long n, int metric, int mode, float scale, float alpha, float eps, float* out3,
                   float* grad, void* stream);
 
+/* rpe_pose_loss over the rows with valid[i] != 0 only (valid: device, n bytes) -- batches cut from episodes of unequal length, whose
+ * padded lanes may hold anything.  A row with valid[i] == 0 is skipped by selection: it adds nothing to any of the three sums, its
+ * grad row is written as +0.0, and neither its pred nor its truth enters any arithmetic (NaN, inf or a zero quaternion there changes
+ * no bit of the result).  A valid row runs the device function rpe_pose_loss runs, in the same thread and order: with an all-ones mask
+ * out3 and grad equal rpe_pose_loss' bit for bit.  All rows masked: out3 = (0, 0, 0). */
+int rpe_pose_loss_masked(const float* pred, const float* truth, const unsigned char* valid, long n, int metric, int mode, float scale, float alpha,
+                         float eps, float* out3, float* grad, void* stream);
+
 /* replaces: the per-sample numpy loop of PoseDistanceLoss's "val" branch (models/losses.py:95-113) as rollout() calls it once per
  * step, and the quaternion normalisation of the printed pose (util/learn_utils.py:451-452,488-489).
  * pred, truth [n][7] fp32.  pos_err[i] = sqrtf(|dp_i|^2 + eps); ori_err[i] = |angle_i| in radians; pose_unit[n][7] (nullable) =
@@ -662,6 +681,12 @@ int rpe_pose_errors(const float* pred, const float* truth, long n, float eps, fl
  * fp64 accumulation in one fixed order by a single workgroup, no atomics: two calls give the same bits.  A NaN in `err`
  * propagates into every figure it takes part in (mean, std, max, its episode's sum and mean). */
 int rpe_error_stats(const float* err, int E, int T, double* out, void* stream);
+/* The same table when row e holds only lengths[e] values (lengths: device, E entries in the order of the rows, each in [1, T]) and the
+ * rest of the row is padding: mean, population standard deviation and maximum run over the sum of the lengths valid values, a row's
+ * sum over its first lengths[e] values and its mean is that sum / lengths[e].  Same layout, same fixed-order fp64 accumulation by one
+ * workgroup without atomics.  Padding is never read into a sum or the maximum (a NaN there is invisible); a NaN in a valid entry
+ * propagates as above.  With every lengths[e] == T the output equals rpe_error_stats' bit for bit. */
+int rpe_error_stats_ragged(const float* err, int E, int T, const int* lengths, double* out, void* stream);
 
 /* replaces: torch.optim.Adam(model.parameters(), lr).step() (scripts/train_model.py:228,
  * util/learn_utils.py:179) over one flat parameter / gradient / moment buffer. */

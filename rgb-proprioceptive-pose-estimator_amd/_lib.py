@@ -130,6 +130,7 @@ _SPEC = {
     "rpe_augment_frames_u8": (I, [P, P, I, I, I, POINTER(AugmentDesc), P, P, P, P]),
     "rpe_augment_depth_f32": (I, [P, P, I, I, I, POINTER(DepthAugmentDesc), P, P, P, I, P]),
     "rpe_sample_windows": (I, [POINTER(SampleDesc), P, P, P, P]),
+    "rpe_sample_windows_ragged": (I, [POINTER(SampleDesc), P, P, P, P, P]),
     "rpe_gather_rows": (I, [P, P, L, L, P, I, I, P]),
     "rpe_measurement_noise": (I, [P, P, POINTER(MeasureDesc), P, P, P]),
     "rpe_bn_finalize": (I, [P, I, I, L, P, P, P, P, P, F, F, P, P, P, P, P, P]),
@@ -174,8 +175,10 @@ _SPEC = {
     "rpe_lstm_cell_fwd": (I, [P, P, P, P, P, P, I, I, P]),
     "rpe_lstm_cell_bwd": (I, [P, P, P, P, P, P, I, I, P]),
     "rpe_pose_loss": (I, [P, P, L, I, I, F, F, F, P, P, P]),
+    "rpe_pose_loss_masked": (I, [P, P, P, L, I, I, F, F, F, P, P, P]),
     "rpe_pose_errors": (I, [P, P, L, F, P, P, P, P]),
     "rpe_error_stats": (I, [P, I, I, P, P]),
+    "rpe_error_stats_ragged": (I, [P, I, I, P, P, P]),
     "rpe_adam_step": (I, [P, P, P, P, L, D, D, D, D, I, P]),
     "rpe_amp_unscale": (I, [P, L, P, P]),
     "rpe_amp_update": (I, [P, F, F, I, P]),

@@ -459,67 +459,69 @@ __device__ __forceinline__ double pose_val_angle(float ip, const float* __restri
 // reference: models/losses.py:47-128.  metric: 0 l2, 1 l1, 2 linf, 3 combined; mode: 0 position, 1 pose.
 // out[0] = loss, out[1] = sum_i sqrt(|dp_i|^2 + eps) (val position error), out[2] = sum_i |angle_i| (val orientation error)
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pose_loss_kernel(const float* __restrict__ pred, const float* __restrict__ truth, long n, int metric,
-                                                       int mode, float scale, float alpha, float eps, float* __restrict__ out,
-                                                       float* __restrict__ grad) {
-    __shared__ double red[3][4];
-    double l_acc = 0.0, p_acc = 0.0, a_acc = 0.0;
-    for (long i = threadIdx.x; i < n; i += blockDim.x) {
-        const float* p = pred + i * 7;
-        const float* t = truth + i * 7;
-        float d[3], ad[3], g[7];
-        const float sq = pose_pos_sq(p, t, d);
+// one sample: its gradient row (when grad is given) and its terms of the three sums; pose_loss_kernel and pose_loss_masked_kernel both
+// run this, a thread over its rows in ascending order
+__device__ __forceinline__ void pose_loss_row(const float* __restrict__ pred, const float* __restrict__ truth, long i, int metric, int mode, float scale,
+                                              float alpha, float eps, float* __restrict__ grad, double& l_acc, double& p_acc, double& a_acc) {
+    const float* p = pred + i * 7;
+    const float* t = truth + i * 7;
+    float d[3], ad[3], g[7];
+    const float sq = pose_pos_sq(p, t, d);
 #pragma unroll
-        for (int k = 0; k < 3; ++k) { ad[k] = fabsf(d[k]); g[k] = 0.f; }
-        const float l2 = sqrtf(sq + eps);
-        float pos = 0.f;
-        if (metric == 0 || metric == 3) {
-            pos += l2;
+    for (int k = 0; k < 3; ++k) { ad[k] = fabsf(d[k]); g[k] = 0.f; }
+    const float l2 = sqrtf(sq + eps);
+    float pos = 0.f;
+    if (metric == 0 || metric == 3) {
+        pos += l2;
 #pragma unroll
-            for (int k = 0; k < 3; ++k) g[k] += d[k] / l2;
-        }
-        if (metric == 1 || metric == 3) {
-            pos += ad[0] + ad[1] + ad[2];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) g[k] += (d[k] > 0.f) ? 1.f : ((d[k] < 0.f) ? -1.f : 0.f);
-        }
-        if (metric == 2 || metric == 3) {
-            int am = 0;  // torch.max(dim) gradient goes to the first maximal index
-            if (ad[1] > ad[am]) am = 1;
-            if (ad[2] > ad[am]) am = 2;
-            pos += ad[am];
-            g[am] += (d[am] > 0.f) ? 1.f : ((d[am] < 0.f) ? -1.f : 0.f);
-        }
-        // quaternion part: qhat = q / |q| (no eps: an all-zero quaternion yields NaN, as in the reference)
-        float h[4], mag;
-        const float ip = pose_unit_quat(p, t, h, mag);
-        const float h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3];
-        float ori = 0.f;
-        float gh[4] = {0.f, 0.f, 0.f, 0.f};  // dL/d qhat
-        if (mode == 1) {
-            ori = (1.f - ip * ip) + fmaxf(-h3, 0.f);
-            const float c = -2.f * ip;
-            gh[0] = c * t[3]; gh[1] = c * t[4]; gh[2] = c * t[5]; gh[3] = c * t[6];
-            if (-h3 >= 0.f) gh[3] -= 1.f;  // torch.clamp(min=0) passes the gradient at the boundary
-        }
-        // d qhat / d q = (I - qhat qhat^T) / |q|
-        // (mode 0, "position": the normalised quaternion is not part of the reference's graph -- models/losses.py:124-126 --
-        // so its gradient is exactly zero, also for an all-zero predicted quaternion where the Jacobian below is 0/0)
-        g[3] = g[4] = g[5] = g[6] = 0.f;
-        if (mode == 1) {
-            const float hd = gh[0] * h0 + gh[1] * h1 + gh[2] * h2 + gh[3] * h3;
-            g[3] = (gh[0] - h0 * hd) / mag; g[4] = (gh[1] - h1 * hd) / mag; g[5] = (gh[2] - h2 * hd) / mag; g[6] = (gh[3] - h3 * hd) / mag;
-        }
-        if (grad) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) grad[i * 7 + k] = scale * g[k];
-#pragma unroll
-            for (int k = 3; k < 7; ++k) grad[i * 7 + k] = scale * alpha * g[k];
-        }
-        l_acc += (double)pos + (double)alpha * (double)ori;
-        p_acc += (double)l2;
-        a_acc += pose_val_angle(ip, t, nullptr);
+        for (int k = 0; k < 3; ++k) g[k] += d[k] / l2;
     }
+    if (metric == 1 || metric == 3) {
+        pos += ad[0] + ad[1] + ad[2];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) g[k] += (d[k] > 0.f) ? 1.f : ((d[k] < 0.f) ? -1.f : 0.f);
+    }
+    if (metric == 2 || metric == 3) {
+        int am = 0;  // torch.max(dim) gradient goes to the first maximal index
+        if (ad[1] > ad[am]) am = 1;
+        if (ad[2] > ad[am]) am = 2;
+        pos += ad[am];
+        g[am] += (d[am] > 0.f) ? 1.f : ((d[am] < 0.f) ? -1.f : 0.f);
+    }
+    // quaternion part: qhat = q / |q| (no eps: an all-zero quaternion yields NaN, as in the reference)
+    float h[4], mag;
+    const float ip = pose_unit_quat(p, t, h, mag);
+    const float h0 = h[0], h1 = h[1], h2 = h[2], h3 = h[3];
+    float ori = 0.f;
+    float gh[4] = {0.f, 0.f, 0.f, 0.f};  // dL/d qhat
+    if (mode == 1) {
+        ori = (1.f - ip * ip) + fmaxf(-h3, 0.f);
+        const float c = -2.f * ip;
+        gh[0] = c * t[3]; gh[1] = c * t[4]; gh[2] = c * t[5]; gh[3] = c * t[6];
+        if (-h3 >= 0.f) gh[3] -= 1.f;  // torch.clamp(min=0) passes the gradient at the boundary
+    }
+    // d qhat / d q = (I - qhat qhat^T) / |q|
+    // (mode 0, "position": the normalised quaternion is not part of the reference's graph -- models/losses.py:124-126 --
+    // so its gradient is exactly zero, also for an all-zero predicted quaternion where the Jacobian below is 0/0)
+    g[3] = g[4] = g[5] = g[6] = 0.f;
+    if (mode == 1) {
+        const float hd = gh[0] * h0 + gh[1] * h1 + gh[2] * h2 + gh[3] * h3;
+        g[3] = (gh[0] - h0 * hd) / mag; g[4] = (gh[1] - h1 * hd) / mag; g[5] = (gh[2] - h2 * hd) / mag; g[6] = (gh[3] - h3 * hd) / mag;
+    }
+    if (grad) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) grad[i * 7 + k] = scale * g[k];
+#pragma unroll
+        for (int k = 3; k < 7; ++k) grad[i * 7 + k] = scale * alpha * g[k];
+    }
+    l_acc += (double)pos + (double)alpha * (double)ori;
+    p_acc += (double)l2;
+    a_acc += pose_val_angle(ip, t, nullptr);
+}
+
+// the threads' partial sums -> out[0..2]: lanes by the xor butterfly, then the four waves in index order
+__device__ __forceinline__ void pose_loss_finish(double l_acc, double p_acc, double a_acc, float scale, float* __restrict__ out) {
+    __shared__ double red[3][4];
     l_acc = wave_sum_d(l_acc); p_acc = wave_sum_d(p_acc); a_acc = wave_sum_d(a_acc);
     if ((threadIdx.x & 63) == 0) { const int wv = threadIdx.x >> 6; red[0][wv] = l_acc; red[1][wv] = p_acc; red[2][wv] = a_acc; }
     __syncthreads();
@@ -528,6 +530,32 @@ __global__ __launch_bounds__(256) void pose_loss_kernel(const float* __restrict_
         out[1] = (float)(red[1][0] + red[1][1] + red[1][2] + red[1][3]);
         out[2] = (float)(red[2][0] + red[2][1] + red[2][2] + red[2][3]);
     }
+}
+
+__global__ __launch_bounds__(256) void pose_loss_kernel(const float* __restrict__ pred, const float* __restrict__ truth, long n, int metric,
+                                                       int mode, float scale, float alpha, float eps, float* __restrict__ out,
+                                                       float* __restrict__ grad) {
+    double l_acc = 0.0, p_acc = 0.0, a_acc = 0.0;
+    for (long i = threadIdx.x; i < n; i += blockDim.x) pose_loss_row(pred, truth, i, metric, mode, scale, alpha, eps, grad, l_acc, p_acc, a_acc);
+    pose_loss_finish(l_acc, p_acc, a_acc, scale, out);
+}
+
+// The same over the rows with valid[i] != 0 only (episodes of unequal length: a padded lane's output may be anything).  A masked row
+// is left out by SELECTION -- neither its pred nor its truth is read, so a NaN there cannot reach a sum as 0 * NaN would -- and its
+// gradient row is +0.  A valid row runs pose_loss_row in the thread and order pose_loss_kernel runs it: an all-ones mask gives its bits.
+__global__ __launch_bounds__(256) void pose_loss_masked_kernel(const float* __restrict__ pred, const float* __restrict__ truth,
+                                                              const unsigned char* __restrict__ valid, long n, int metric, int mode, float scale,
+                                                              float alpha, float eps, float* __restrict__ out, float* __restrict__ grad) {
+    double l_acc = 0.0, p_acc = 0.0, a_acc = 0.0;
+    for (long i = threadIdx.x; i < n; i += blockDim.x) {
+        if (valid[i]) {
+            pose_loss_row(pred, truth, i, metric, mode, scale, alpha, eps, grad, l_acc, p_acc, a_acc);
+        } else if (grad) {
+#pragma unroll
+            for (int k = 0; k < 7; ++k) grad[i * 7 + k] = 0.f;
+        }
+    }
+    pose_loss_finish(l_acc, p_acc, a_acc, scale, out);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -602,6 +630,49 @@ __global__ __launch_bounds__(256) void error_stats_kernel(const float* __restric
     if (threadIdx.x == 0) {
         out[0] = mean;
         out[1] = sqrt(q / (double)total);
+        out[2] = nan_max_d(nan_max_d(red[0], red[1]), nan_max_d(red[2], red[3]));
+    }
+}
+
+// The same statistics over the first len_e = clamp(lengths[e], 0, T) values of every row only (episodes of unequal length; the rest of
+// a row is padding and is never read into a sum or the maximum).  The walk is error_stats_kernel's -- the same threads meet the same
+// elements in the same order and skip the padded ones -- so with every len_e == T the output has its bits.
+__global__ __launch_bounds__(256) void error_stats_ragged_kernel(const float* __restrict__ err, int E, int T, const int* __restrict__ lengths,
+                                                                double* __restrict__ out) {
+    __shared__ double red[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const long total = (long)E * T;
+    double* row_sum = out + 3;
+    double* row_mean = out + 3 + E;
+    for (int e = wv; e < E; e += 4) {
+        const int len = min(max(lengths[e], 0), T);
+        double s = 0.0;
+        for (int t = lane; t < len; t += 64) s += (double)err[(long)e * T + t];
+        s = wave_sum_d(s);
+        if (lane == 0) { row_sum[e] = s; row_mean[e] = s / (double)len; }
+    }
+    __syncthreads();   // the row sums just stored are read back below by other threads of this workgroup
+    double s = 0.0, c = 0.0;   // (the count of valid values as a double: integers below 2^53, so the sum is exact in any order)
+    for (int e = threadIdx.x; e < E; e += 256) { s += row_sum[e]; c += (double)min(max(lengths[e], 0), T); }
+    const double count = block_sum_d(c, red);
+    const double mean = block_sum_d(s, red) / count;
+    double q = 0.0, m = -INFINITY;
+    for (long i = threadIdx.x; i < total; i += 256) {
+        const long e = i / T;
+        if ((int)(i - e * T) >= lengths[e]) continue;
+        const double x = (double)err[i];
+        const double dv = x - mean;
+        q += dv * dv;
+        m = nan_max_d(m, x);
+    }
+    q = block_sum_d(q, red);
+    for (int o = 32; o > 0; o >>= 1) m = nan_max_d(m, __shfl_xor(m, o));
+    __syncthreads();
+    if (lane == 0) red[wv] = m;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        out[0] = mean;
+        out[1] = sqrt(q / count);
         out[2] = nan_max_d(nan_max_d(red[0], red[1]), nan_max_d(red[2], red[3]));
     }
 }
@@ -1197,6 +1268,17 @@ int rpe_pose_loss(const float* pred, const float* truth, long n, int metric, int
     return 0;
 }
 
+int rpe_pose_loss_masked(const float* pred, const float* truth, const unsigned char* valid, long n, int metric, int mode, float scale, float alpha,
+                         float eps, float* out3, float* grad, void* stream) {
+    if (metric < 0 || metric > 3 || mode < 0 || mode > 1) return rpe_set_error(RPE_ERR_SHAPE, "pose_loss_masked: invalid metric/mode");
+    if (n <= 0) return rpe_set_error(RPE_ERR_SHAPE, "pose_loss_masked: empty batch");
+    if (!pred || !truth || !valid || !out3) return rpe_set_error(RPE_ERR_SHAPE, "pose_loss_masked: pred, truth, valid and out3 are required");
+    hipLaunchKernelGGL(pose_loss_masked_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, pred, truth, valid, n, metric, mode, scale, alpha, eps, out3,
+                       grad);
+    RPE_CHECK_LAUNCH();
+    return 0;
+}
+
 int rpe_pose_errors(const float* pred, const float* truth, long n, float eps, float* pos_err, float* ori_err, float* pose_unit, void* stream) {
     if (n <= 0) return rpe_set_error(RPE_ERR_SHAPE, "pose_errors: empty batch");
     if (!pred || !truth || !pos_err || !ori_err) return rpe_set_error(RPE_ERR_SHAPE, "pose_errors: pred, truth, pos_err and ori_err are required");
@@ -1209,6 +1291,14 @@ int rpe_error_stats(const float* err, int E, int T, double* out, void* stream) {
     if (E <= 0 || T <= 0) return rpe_set_error(RPE_ERR_SHAPE, "error_stats: E and T must be positive");
     if (!err || !out) return rpe_set_error(RPE_ERR_SHAPE, "error_stats: err and out are required");
     hipLaunchKernelGGL(error_stats_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, err, E, T, out);
+    RPE_CHECK_LAUNCH();
+    return 0;
+}
+
+int rpe_error_stats_ragged(const float* err, int E, int T, const int* lengths, double* out, void* stream) {
+    if (E <= 0 || T <= 0) return rpe_set_error(RPE_ERR_SHAPE, "error_stats_ragged: E and T must be positive");
+    if (!err || !lengths || !out) return rpe_set_error(RPE_ERR_SHAPE, "error_stats_ragged: err, lengths and out are required");
+    hipLaunchKernelGGL(error_stats_ragged_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, err, E, T, lengths, out);
     RPE_CHECK_LAUNCH();
     return 0;
 }

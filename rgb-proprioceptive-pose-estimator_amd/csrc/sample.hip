@@ -4,6 +4,7 @@
 //   sample_index_kernel : reads the step counter state[0], writes index[0] = step and the (episode, first timestep) of the step's N
 //                         windows, advances the counter -- the only reader and writer of `state`, so a captured launch draws the next
 //                         batch at every replay
+//   sample_index_ragged_kernel : the same for episodes of unequal length; the window table is scanned on the device at every launch
 //   gather_rows_kernel  : out row s N + n <- pool row episode[n] T + t0[n] + s, rows of row_bytes bytes; one kernel for frames, depth,
 //                         poses and measurements
 // All arithmetic is unsigned / 64-bit integer.  The shuffle is a keyed bijection of [0, M): a 4-round balanced Feistel network over
@@ -47,6 +48,79 @@ __global__ void __launch_bounds__(256) sample_index_kernel(unsigned* __restrict_
         const unsigned e = w / K;
         index[1 + 2 * i] = sel[e];
         index[2 + 2 * i] = (int)((w - e * K) * (unsigned)d.stride);
+    }
+    if (threadIdx.x == 0) {
+        index[0] = (int)step;
+        state[0] = step + 1u;
+    }
+}
+
+// ---- episodes of unequal length ----------------------------------------------------------------------------------------------
+// The same draw over windows that no longer form an E x K grid: episode e of the selection has len_e = clamp(lengths[sel[e]], 0, T)
+// timesteps and K_e = len_e >= S ? (len_e - S) / stride + 1 : 0 start positions; P_e = K_0 + .. + K_{e-1} and M = P_E.  `lengths` and
+// `sel` are read at every launch, so M -- and with it the domain of the keyed permutation -- belongs to the launch, not to the host:
+// the block scans the K_e into LDS (every thread a run of consecutive episodes, the runs' totals through the wave and the four waves),
+// takes the Feistel half width from this M, and finds a window's episode by binary search, the largest e with P_e <= w.
+constexpr int kRaggedMaxEpisodes = 8192;   // the prefix table: 32 KB of LDS
+
+__global__ void __launch_bounds__(256) sample_index_ragged_kernel(unsigned* __restrict__ state, int* __restrict__ index, const int* __restrict__ sel,
+                                                                 const int* __restrict__ lengths, rpe_sample_desc d) {
+    __shared__ unsigned P[kRaggedMaxEpisodes];   // P[e]: windows in front of episode e
+    __shared__ unsigned wsum[4];
+    const unsigned step = state[0];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int per = (d.E + 255) / 256, e0 = (int)threadIdx.x * per, e1 = e0 + per < d.E ? e0 + per : d.E;
+    unsigned run = 0;
+    for (int e = e0; e < e1; ++e) {
+        int len = lengths[sel[e]];
+        len = len < 0 ? 0 : (len > d.T ? d.T : len);
+        P[e] = run;
+        run += len >= d.S ? (unsigned)(len - d.S) / (unsigned)d.stride + 1u : 0u;
+    }
+    unsigned inc = run;   // inclusive scan of the runs' totals along the wave
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned v = __shfl_up(inc, o);
+        if (lane >= o) inc += v;
+    }
+    if (lane == 63) wsum[wv] = inc;
+    __syncthreads();   // the waves' totals are stored; every thread has read the counter before it moves
+    unsigned base = inc - run;
+    for (int w = 0; w < wv; ++w) base += wsum[w];
+    for (int e = e0; e < e1; ++e) P[e] += base;
+    const unsigned M = wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    __syncthreads();   // the table is complete
+    const int bits = M > 1u ? 32 - __clz(M - 1u) : 0;   // bit length of M - 1
+    const int h = ((bits > 2 ? bits : 2) + 1) / 2;
+    const unsigned k0 = (unsigned)d.seed, k1 = (unsigned)(d.seed >> 32), mask = (1u << h) - 1u;
+    for (int i = threadIdx.x; i < d.N; i += 256) {
+        if (M == 0u) {   // no window at all: in bounds for the gather, and meaningless
+            index[1 + 2 * i] = sel[0];
+            index[2 + 2 * i] = 0;
+            continue;
+        }
+        const u64 g = (u64)step * (u64)d.N + (u64)i;
+        const u64 epoch = g / M;
+        unsigned w = (unsigned)(g - epoch * M);
+        if (d.shuffle && M > 1) {
+            do {   // ends: w lies on the cycle through pos < M
+                unsigned L = w >> h, R = w & mask;
+#pragma unroll
+                for (unsigned r = 0; r < 4; ++r) {
+                    unsigned f[4];
+                    philox4x32_10(R, r, (unsigned)epoch, kSamplePurpose, k0, k1, f);
+                    const unsigned t = L ^ (f[0] & mask);
+                    L = R; R = t;
+                }
+                w = (L << h) | R;
+            } while (w >= M);
+        }
+        int lo = 0, hi = d.E - 1;   // P[lo] <= w throughout (P[0] = 0)
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (P[mid] <= w) lo = mid; else hi = mid - 1;
+        }
+        index[1 + 2 * i] = sel[lo];
+        index[2 + 2 * i] = (int)((w - P[lo]) * (unsigned)d.stride);
     }
     if (threadIdx.x == 0) {
         index[0] = (int)step;
@@ -106,6 +180,20 @@ extern "C" int rpe_sample_windows(const rpe_sample_desc* d, const int* sel, unsi
     const int h = ((bits > 2 ? bits : 2) + 1) / 2;
     note_kernel("sample_index_kernel");
     hipLaunchKernelGGL(sample_index_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, state, index, sel, *d, (unsigned)K, (unsigned)M, h);
+    RPE_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int rpe_sample_windows_ragged(const rpe_sample_desc* d, const int* sel, const int* lengths, unsigned* state, int* index, void* stream) {
+    if (!d || !sel || !lengths || !state || !index) return rpe_set_error(RPE_ERR_SHAPE, "sample_windows_ragged: null pointer");
+    if (d->E < 1 || d->T < 1 || d->S < 1 || d->stride < 1 || d->N < 1) return rpe_set_error(RPE_ERR_SHAPE, "sample_windows_ragged: E, T, S, stride and N must be at least 1");
+    if (d->S > d->T) return rpe_set_error(RPE_ERR_SHAPE, "sample_windows_ragged: a window of S timesteps needs S <= T");
+    if (d->shuffle != 0 && d->shuffle != 1) return rpe_set_error(RPE_ERR_SHAPE, "sample_windows_ragged: shuffle is 0 (file order) or 1 (keyed permutation)");
+    if (d->E > kRaggedMaxEpisodes) return rpe_set_error(RPE_ERR_SHAPE, "sample_windows_ragged: at most 8192 selected episodes (the prefix table lives in LDS)");
+    const long K = (long)(d->T - d->S) / d->stride + 1;   // the most any episode can have
+    if ((long)d->E * K >= (1L << 31)) return rpe_set_error(RPE_ERR_SHAPE, "sample_windows_ragged: E * max K windows must stay below 2^31");
+    note_kernel("sample_index_ragged_kernel");
+    hipLaunchKernelGGL(sample_index_ragged_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, state, index, sel, lengths, *d);
     RPE_CHECK_LAUNCH();
     return 0;
 }

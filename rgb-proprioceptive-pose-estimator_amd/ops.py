@@ -587,12 +587,29 @@ def copy2d(src, dst, cols=None):
     return dst
 
 
-def pose_loss(pred, truth, metric, mode, scale, alpha, eps, want_grad=True):
-    """pred/truth (..., 7) fp32 contiguous -> (out3 [loss, val_pos, val_ori], grad or None)."""
+def pose_loss(pred, truth, metric, mode, scale, alpha, eps, want_grad=True, valid=None):
+    """pred/truth (..., 7) fp32 contiguous -> (out3 [loss, val_pos, val_ori], grad or None).
+    valid (uint8 or bool device tensor of pred.shape[:-1], contiguous): only the rows it marks take part (rpe_pose_loss_masked) -- the
+    others are never read, add nothing and get a +0 gradient row."""
     n = pred.numel() // 7
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.uint8, torch.bool) or tuple(valid.shape) != tuple(pred.shape[:-1]):
+            raise ValueError("pose_loss: valid must be a uint8 or bool tensor of shape %r; got %s %r" % (
+                tuple(pred.shape[:-1]), getattr(valid, "dtype", type(valid)), tuple(getattr(valid, "shape", ()))))
+        if valid.device != pred.device or not valid.is_cuda:
+            raise ValueError("pose_loss: valid must be on the device of pred (%s); got %s" % (pred.device, valid.device))
+        if pred.dtype != torch.float32 or truth.dtype != torch.float32 or truth.device != pred.device:
+            raise ValueError("pose_loss: pred and truth must be fp32 on one device")
+        _chk(valid, "valid")
+        if valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)   # (one byte each, 0 / 1: the same memory)
     out3 = torch.empty(3, dtype=torch.float32, device=pred.device)
     grad = torch.empty_like(pred) if want_grad else None
-    lib.rpe_pose_loss(_p(_chk(pred, "pred")), _p(_chk(truth, "truth")), n, metric, mode, scale, alpha, eps, _p(out3), _p(grad), _stream())
+    if valid is None:
+        lib.rpe_pose_loss(_p(_chk(pred, "pred")), _p(_chk(truth, "truth")), n, metric, mode, scale, alpha, eps, _p(out3), _p(grad), _stream())
+    else:
+        lib.rpe_pose_loss_masked(_p(_chk(pred, "pred")), _p(_chk(truth, "truth")), _p(valid), n, metric, mode, scale, alpha, eps, _p(out3), _p(grad),
+                                 _stream())
     return out3, grad
 
 
@@ -611,14 +628,26 @@ def pose_errors(pred, truth, eps, want_pose=True):
     return pos, ori, pose
 
 
-def error_stats(err):
+def error_stats(err, lengths=None):
     """err (E, T) fp32 contiguous -> fp64 device tensor of 3 + 2 E values: [mean, population std, max, sum[E], mean[E]]
-    (rpe_error_stats: fixed-order fp64 sums, bitwise repeatable, NaN propagates)."""
+    (rpe_error_stats: fixed-order fp64 sums, bitwise repeatable, NaN propagates).
+    lengths (int32 device tensor (E,), each in [1, T]): row e holds lengths[e] values and padding behind them, which is never read
+    (rpe_error_stats_ragged); the figures run over the valid values only."""
     if err.dim() != 2 or err.dtype != torch.float32:
         raise ValueError("error_stats: err must be an fp32 (E, T) tensor, got %s %s" % (err.dtype, tuple(err.shape)))
     e, t = err.shape
+    if lengths is not None:
+        if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or tuple(lengths.shape) != (e,):
+            raise ValueError("error_stats: lengths must be an int32 tensor of shape (%d,); got %s %r" % (
+                e, getattr(lengths, "dtype", type(lengths)), tuple(getattr(lengths, "shape", ()))))
+        if lengths.device != err.device or not lengths.is_cuda:
+            raise ValueError("error_stats: lengths must be on the device of err (%s); got %s" % (err.device, lengths.device))
+        _chk(lengths, "lengths")
     out = torch.empty(3 + 2 * e, dtype=torch.float64, device=err.device)
-    lib.rpe_error_stats(_p(_chk(err, "err")), e, t, _p(out), _stream())
+    if lengths is None:
+        lib.rpe_error_stats(_p(_chk(err, "err")), e, t, _p(out), _stream())
+    else:
+        lib.rpe_error_stats_ragged(_p(_chk(err, "err")), e, t, _p(lengths), _p(out), _stream())
     return out
 
 
@@ -940,6 +969,30 @@ def sample_windows(desc, sel, state, out=None):
     elif out.dtype != torch.int32 or out.numel() < n or out.device != dev:
         raise ValueError("sample_windows: out must be int32 with at least %d elements on sel's device" % n)
     lib.rpe_sample_windows(ctypes.byref(desc), _p(_chk(sel, "sel")), _p(_chk(state, "state")), _p(_chk(out, "out")), _stream())
+    return out
+
+
+def sample_windows_ragged(desc, sel, lengths, state, out=None):
+    """sample_windows over episodes of unequal length (rpe_sample_windows_ragged): lengths, an int32 device tensor with one entry per
+    episode IN THE FILE, is read as lengths[sel[e]] at every launch; a window never leaves its episode's lengths[sel[e]] timesteps, and
+    an episode shorter than desc.S is never drawn.  At most 8192 selected episodes.  The rest as sample_windows."""
+    dev = sel.device
+    if sel.dtype != torch.int32 or sel.dim() != 1 or sel.numel() < desc.E:
+        raise ValueError("sample_windows_ragged: sel must be an int32 vector of at least E = %d episode numbers" % desc.E)
+    if not isinstance(lengths, torch.Tensor) or lengths.dtype != torch.int32 or lengths.dim() != 1 or lengths.numel() < 1:
+        raise ValueError("sample_windows_ragged: lengths must be an int32 vector, one entry per episode in the file; got %s" % (
+            getattr(lengths, "dtype", type(lengths)),))
+    if lengths.device != dev or not lengths.is_cuda:
+        raise ValueError("sample_windows_ragged: lengths must be on sel's device (%s); got %s" % (dev, lengths.device))
+    if state.dtype != torch.int32 or state.numel() < 1 or state.device != dev:
+        raise ValueError("sample_windows_ragged: state must be an int32 tensor on sel's device")
+    n = 1 + 2 * max(int(desc.N), 0)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=dev)
+    elif out.dtype != torch.int32 or out.numel() < n or out.device != dev:
+        raise ValueError("sample_windows_ragged: out must be int32 with at least %d elements on sel's device" % n)
+    lib.rpe_sample_windows_ragged(ctypes.byref(desc), _p(_chk(sel, "sel")), _p(_chk(lengths, "lengths")), _p(_chk(state, "state")), _p(_chk(out, "out")),
+                                  _stream())
     return out
 
 

@@ -13,7 +13,8 @@ the model resizes, crops and normalises on the device.
 
 `--batched` scores all episodes in one batched pass instead (util.learn_utils.evaluate_episodes: the episodes advance together as
 lanes of one batch, per-step errors and their statistics are computed on the device) and prints the reference's summary lines;
-`--noise_scales` scores the same frames under several measurement-noise scales with one trunk pass.
+`--noise_scales` scores the same frames under several measurement-noise scales with one trunk pass.  An `--episodes` file of episodes
+of unequal length (a `lengths` array) is scored this way only: `--errors_out` gains `lengths`, the entries behind an episode's end are NaN.
 
 `--video_out FILE.gif|FILE.npy` (needs `--episodes` and `--camera_matrix FILE.npy`; implies `--batched`) is the reference's recorded
 video without the simulator: the estimated and the true pose are projected through the camera's matrix and drawn on the recorded
@@ -70,6 +71,14 @@ def main(argv=None):
     from rgb_proprioceptive_pose_estimator_amd.models import PoseDistanceLoss
     from rgb_proprioceptive_pose_estimator_amd.util.data_utils import RecordedEpisodeDataset, synthetic_batch
 
+    if args.episodes and (not args.batched or args.model_outputs_file):   # episodes of unequal length are scored by evaluate_episodes only
+        try:
+            ragged = RecordedEpisodeDataset.file_lengths(args.episodes) is not None
+        except (OSError, ValueError):
+            ragged = False   # (the dataset reports an unreadable file)
+        if ragged:
+            raise SystemExit("rollout.py: {} holds episodes of unequal length; the frame-by-frame walk and --model_outputs_file do not know padding: "
+                             "use --batched (alone, or with --video_out)".format(args.episodes))
     np.random.seed(3)
     torch.manual_seed(3)
     if not torch.cuda.is_available():
@@ -202,8 +211,9 @@ def write_episode_video(res, dataset, video):
     part = types.SimpleNamespace(poses=lead(res.poses), pos_err=lead(res.pos_err), ori_err=lead(res.ori_err), truth=None if res.truth is None else res.truth[:n],
                                  measurements=lead(res.measurements), noise_scales=res.noise_scales)
     pictures = render_episodes(part, dataset.data["imgs"][:n], video["camera"], **video["kwargs"])
-    write_video(pictures, video["out"], fps=video["fps"])
-    print("wrote {} frames to {}".format(pictures.shape[0] * pictures.shape[1], video["out"]))
+    lengths = None if getattr(res, "lengths", None) is None else res.lengths[:n]   # episodes of unequal length: the padding is not written
+    write_video(pictures, video["out"], fps=video["fps"], lengths=lengths)
+    print("wrote {} frames to {}".format(pictures.shape[0] * pictures.shape[1] if lengths is None else int(lengths.sum()), video["out"]))
     return pictures
 
 
@@ -233,7 +243,8 @@ def batched(args, model, video=None):
     if args.errors_out:
         with open(args.errors_out, "wb") as f:   # (np.savez would append ".npz" to a bare name)
             np.savez(f, pos_err=res.pos_err.cpu().numpy(), ori_err=res.ori_err.cpu().numpy(), poses=res.poses.cpu().numpy(),
-                     noise_scales=np.asarray([args.noise_scale] if args.noise_scales is None else args.noise_scales, dtype=np.float64))
+                     noise_scales=np.asarray([args.noise_scale] if args.noise_scales is None else args.noise_scales, dtype=np.float64),
+                     **({} if res.lengths is None else {"lengths": res.lengths}))
     print(res.summary())
     if video is not None:
         write_episode_video(res, dataset, video)

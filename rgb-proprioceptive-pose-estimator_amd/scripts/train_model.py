@@ -12,7 +12,7 @@ the on-device frame augmentation of recorded episodes (--aug_brightness, --aug_c
 --aug_erase_prob, --aug_erase_scale, --aug_erase_fill, --aug_per_frame, --aug_seed; all off by default, they need --episodes) and of
 their depth frames (--aug_depth_noise, --aug_depth_drop_prob, --aug_depth_holes, --aug_depth_hole_scale, --aug_depth_hole_value,
 --aug_depth_quant, --aug_depth_clamp, --aug_depth_share_erase, --aug_depth_occluder_value; off by default, they need --use_depth --episodes);
---resident (the --episodes file lives in HBM) and, with it, --batch_size, --window_stride, --shuffle_seed (shuffled minibatches drawn on the
+--resident (the --episodes file lives in HBM; an --episodes file of episodes of unequal length needs it and --batch_size) and, with it, --batch_size, --window_stride, --shuffle_seed (shuffled minibatches drawn on the
 device instead of one chunk of every episode per step); --meas_noise_device / --meas_noise_scales, --meas_noise_correlation,
 --meas_noise_seed (the measurement noise of the `train` phase drawn on the device, fresh at every step; off by default, any dataset).
 
@@ -323,11 +323,27 @@ def build_optimizer(args, params):
     return torch.optim.Adam(params, lr=args.lr)
 
 
+def check_ragged(args, sampling):
+    """--episodes with a `lengths` array (episodes of unequal length) trains from shuffled minibatches only: without --resident
+    --batch_size the run stops here, before anything is built"""
+    if not getattr(args, "episodes", None) or sampling:
+        return
+    from rgb_proprioceptive_pose_estimator_amd.util.data_utils import RecordedEpisodeDataset
+    try:
+        lengths = RecordedEpisodeDataset.file_lengths(args.episodes)
+    except (OSError, ValueError):
+        return   # (the dataset reports an unreadable file)
+    if lengths is not None:
+        raise SystemExit("{} holds episodes of unequal length: they train from shuffled minibatches, which never draw padding -- give "
+                         "--resident --batch_size B".format(args.episodes))
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     build_depth_augment(args, augment=build_augment(args))   # (a flag that cannot be honoured stops the run before anything is built)
     sampling = build_sampling(args)
     build_measurement_noise(args)
+    check_ragged(args, sampling)
     from rgb_proprioceptive_pose_estimator_amd.dist import init_from_env
     from rgb_proprioceptive_pose_estimator_amd.models import PoseDistanceLoss
     from rgb_proprioceptive_pose_estimator_amd.util.data_utils import RecordedEpisodeDataset, ResidentEpisodeDataset, SyntheticEpisodeDataset

@@ -20,6 +20,8 @@ ResNet; models/losses.py:114-128 is the loss; util/learn_utils.py:152-184 the st
     rpe::augment_frames_u8                          (no counterpart: the reference does not augment) jitter, noise and erasing of raw uint8 frames
     rpe::augment_depth_f32                          (no counterpart) depth-sensor model on raw fp32 depth: range noise, quantisation, clamp, dropout, holes, the RGB occluder
     rpe::sample_windows / gather_rows               DataLoader(shuffle=True) over episode windows resident in HBM: the batch's index, and its rows
+    rpe::sample_windows_ragged / pose_loss_masked / (no counterpart: the reference's episodes all have one length) the window index, the summed loss and the
+    rpe::error_stats_ragged                         error statistics of episodes of unequal length, padded to one horizon: padding is never drawn or read
     rpe::measurement_noise                          x0 + sqrt(scale) * randn_like(x0) with the quaternion renormalised (util/data_utils.py:162-167), drawn on the device
     rpe::occlude_grid_u8 / pose_displacement /      (no counterpart: occlusion sensitivity) a frame with one rectangle of a grid covered per row; how far
     rpe::saliency_map / saliency_overlay_u8         each prediction moved; the scores spread over the pixels; the map drawn over the frame
@@ -37,7 +39,7 @@ __all__ = ["NAMES"]
 
 _NS = "rpe"
 NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step", "augment_frames_u8", "augment_depth_f32", "sample_windows", "gather_rows",
-         "measurement_noise", "occlude_grid_u8", "pose_displacement", "saliency_map", "saliency_overlay_u8", "param_stats", "project_poses", "draw_poses_u8")
+         "sample_windows_ragged", "pose_loss_masked", "error_stats_ragged", "measurement_noise", "occlude_grid_u8", "pose_displacement", "saliency_map", "saliency_overlay_u8", "param_stats", "project_poses", "draw_poses_u8")
 
 
 def _ops():
@@ -262,6 +264,45 @@ def gather_rows(pool: torch.Tensor, index: torch.Tensor, S: int, T: int) -> torc
 @gather_rows.register_fake
 def _(pool, index, S, T):
     return pool.new_empty((S, (index.shape[0] - 1) // 2) + tuple(pool.shape[2:]))
+
+
+# ---- episodes of unequal length ------------------------------------------------------------------------------------------------
+@torch.library.custom_op(_NS + "::sample_windows_ragged", mutates_args=("state",), device_types="cuda")
+def sample_windows_ragged(desc: List[int], sel: torch.Tensor, lengths: torch.Tensor, state: torch.Tensor) -> torch.Tensor:
+    """rpe::sample_windows when episode sel[e] has only lengths[sel[e]] timesteps; lengths: int32, one entry per episode in the file"""
+    ops = _ops()
+    if len(desc) != len(ops.SAMPLE_DESC_FIELDS):
+        raise ValueError("sample_windows_ragged: desc has %d integers (%s)" % (len(ops.SAMPLE_DESC_FIELDS), ", ".join(ops.SAMPLE_DESC_FIELDS)))
+    return ops.sample_windows_ragged(ops.sample_desc(**dict(zip(ops.SAMPLE_DESC_FIELDS, desc))), sel, lengths, state)
+
+
+@sample_windows_ragged.register_fake
+def _(desc, sel, lengths, state):
+    return sel.new_empty((1 + 2 * desc[5],))
+
+
+@torch.library.custom_op(_NS + "::pose_loss_masked", mutates_args=(), device_types="cuda")
+def pose_loss_masked(pred: torch.Tensor, truth: torch.Tensor, valid: torch.Tensor, metric: int, mode: int, scale: float, alpha: float,
+                     eps: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """rpe::pose_loss over the rows valid (uint8 or bool, pred.shape[:-1]) marks; the other rows are never read and get a +0 gradient"""
+    out3, grad = _ops().pose_loss(pred, truth, metric, mode, scale, alpha, eps, want_grad=True, valid=valid)
+    return out3, grad
+
+
+@pose_loss_masked.register_fake
+def _(pred, truth, valid, metric, mode, scale, alpha, eps):
+    return pred.new_empty((3,)), torch.empty_like(pred)
+
+
+@torch.library.custom_op(_NS + "::error_stats_ragged", mutates_args=(), device_types="cuda")
+def error_stats_ragged(err: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
+    """err fp32 (E, T), lengths int32 (E,) -> fp64 (3 + 2 E,): mean, population std, max over the valid values, then per-row sums and means"""
+    return _ops().error_stats(err, lengths)
+
+
+@error_stats_ragged.register_fake
+def _(err, lengths):
+    return err.new_empty((3 + 2 * err.shape[0],), dtype=torch.float64)
 
 
 # ---- measurement noise ---------------------------------------------------------------------------------------------------------

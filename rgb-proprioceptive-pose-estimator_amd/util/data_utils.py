@@ -194,6 +194,12 @@ class RecordedEpisodeDataset(_TimestepItems):
         true_other (E, T, 7) float32            optional; needed for a two-arm environment
         true_obj   (E, T, 7) float32            optional; needed for obj_name
         env_name   string                       optional, default "Recorded"; "TwoArm" in it means two arms, as in the reference
+        lengths    (E,) int32 or int64          optional; 1 <= lengths[e] <= T: episode e has lengths[e] timesteps, and rows
+                                                [lengths[e], T) of its per-step arrays are padding that never influences a result
+
+    A file without `lengths` is dense: every episode has T timesteps, `lengths` is None here and nothing below applies.  With it,
+    `len(dataset)` and `env.horizon` stay T, the padded horizon; after refresh_data `selected_lengths` (host) and data["lengths"] hold
+    the lengths of the selection, and `valid(t0, S)` marks the rows of a lockstep chunk that exist.
 
     The data stays on the HOST: `__getitem__(t)` hands out the reference's 6-tuple of host tensors with frames and depth raw, and
     train() moves them through FramePrefetcher; resize, crop and normalisation run on the device (rpe_stage_frames_u8[_resized],
@@ -208,6 +214,10 @@ class RecordedEpisodeDataset(_TimestepItems):
             arrays = {k: f[k] for k in f.files}
         env_name = str(arrays.pop("env_name")) if "env_name" in arrays else "Recorded"
         self._check(arrays)
+        lengths = arrays.pop("lengths", None)
+        self.lengths = None if lengths is None else lengths.astype(np.int64)   # host, per episode in the file; None: a dense file
+        self.selected_lengths = None
+        self._valid_lengths = None          # the selection's lengths on the device valid() builds its masks on
         self.is_two_arm = "TwoArm" in env_name
         if use_depth and "depths" not in arrays:
             raise ValueError("{}: use_depth needs the 'depths' array".format(path))
@@ -225,12 +235,18 @@ class RecordedEpisodeDataset(_TimestepItems):
         self.env = type(env_name, (), {})()
         self.env.horizon = arrays["imgs"].shape[1]
 
+    @staticmethod
+    def file_lengths(path):
+        """the `lengths` array of an episode file, or None for a dense one; reads nothing else of the file"""
+        with np.load(path, allow_pickle=False) as f:
+            return f["lengths"] if "lengths" in f.files else None
+
     @classmethod
     def _check(cls, arrays):
         """ValueError unless the arrays have the file format's ranks, dtypes and matching leading dimensions"""
-        unknown = set(arrays) - {"imgs", "depths"} - set(cls._POSES)
+        unknown = set(arrays) - {"imgs", "depths", "lengths"} - set(cls._POSES)
         if unknown:
-            raise ValueError("unknown arrays {}: the file holds imgs, depths, true_self, true_other, true_obj, env_name".format(sorted(unknown)))
+            raise ValueError("unknown arrays {}: the file holds imgs, depths, true_self, true_other, true_obj, lengths, env_name".format(sorted(unknown)))
         for need in ("imgs", "true_self"):
             if need not in arrays:
                 raise ValueError("the '{}' array is required".format(need))
@@ -244,16 +260,53 @@ class RecordedEpisodeDataset(_TimestepItems):
         for k in cls._POSES:
             if k in arrays and (arrays[k].dtype != np.float32 or arrays[k].shape != imgs.shape[:2] + (7,)):
                 raise ValueError("{} must be float32 {}; got {} {}".format(k, imgs.shape[:2] + (7,), arrays[k].dtype, arrays[k].shape))
+        if "lengths" in arrays:
+            n = arrays["lengths"]
+            if n.dtype not in (np.int32, np.int64) or n.shape != imgs.shape[:1]:
+                raise ValueError("lengths must be int32 or int64 {}; got {} {}".format(imgs.shape[:1], n.dtype, n.shape))
+            bad = np.flatnonzero((n < 1) | (n > imgs.shape[1]))
+            if bad.size:
+                raise ValueError("lengths must lie in [1, T = {}]; got {} for episode {}".format(imgs.shape[1], int(n[bad[0]]), int(bad[0])))
 
     @classmethod
-    def save(cls, path, env_name="Recorded", **arrays):
+    def save(cls, path, env_name="Recorded", lengths=None, **arrays):
         """Write an episode file: imgs=, true_self= and optionally depths=, true_other=, true_obj= (numpy arrays or tensors), checked
-        against the format above."""
+        against the format above.  lengths= (E,) integers: the episodes' numbers of timesteps when the arrays are padded to one T."""
+        arrays["lengths"] = lengths
         arrays = {k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in arrays.items() if v is not None}
         cls._check(arrays)
         with open(path, "wb") as f:   # (np.savez would append ".npz" to a bare name)
             np.savez(f, env_name=np.array(str(env_name)), **arrays)
         return path
+
+    @classmethod
+    def pack(cls, path, episodes, env_name="Recorded"):
+        """Write episodes of unequal length as one file: `episodes` is a list of dicts of per-step arrays without the episode
+        dimension -- imgs (T_e, Hs, Ws, 3), true_self (T_e, 7), ... -- which are padded with zeros to the longest and written with
+        `lengths`.  ValueError when the keys, the dtypes or the frame geometry differ between episodes."""
+        eps = [{k: (v.cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)) for k, v in ep.items() if v is not None} for ep in episodes]
+        if not eps:
+            raise ValueError("pack: no episodes")
+        first = eps[0]
+        lengths = []
+        for i, ep in enumerate(eps):
+            if set(ep) != set(first):
+                raise ValueError("pack: episode {} holds {}, episode 0 holds {}".format(i, sorted(ep), sorted(first)))
+            steps = {v.shape[0] if v.ndim else -1 for v in ep.values()}
+            if len(steps) != 1 or min(steps) < 1:
+                raise ValueError("pack: the arrays of episode {} must share one number of timesteps, at least 1; got {}".format(
+                    i, {k: v.shape[:1] for k, v in ep.items()}))
+            for k, v in ep.items():
+                if v.dtype != first[k].dtype or v.shape[1:] != first[k].shape[1:]:
+                    raise ValueError("pack: {} of episode {} is {} {} per step, of episode 0 {} {}".format(
+                        k, i, v.dtype, v.shape[1:], first[k].dtype, first[k].shape[1:]))
+            lengths.append(steps.pop())
+        t = max(lengths)
+        arrays = {k: np.zeros((len(eps), t) + first[k].shape[1:], dtype=first[k].dtype) for k in first}
+        for i, ep in enumerate(eps):
+            for k, v in ep.items():
+                arrays[k][i, :lengths[i]] = v
+        return cls.save(path, env_name=env_name, lengths=np.asarray(lengths, dtype=np.int32), **arrays)
 
     def _select(self, num_episodes):
         """-> the numbers of the next `num_episodes` episodes in file order, wrapping around (also kept as the list `selected`)"""
@@ -262,7 +315,36 @@ class RecordedEpisodeDataset(_TimestepItems):
         sel = (torch.arange(num_episodes) + self._next) % self.num_recorded
         self._next = int(self._next + num_episodes) % self.num_recorded
         self.selected = sel.tolist()
+        if self.lengths is not None:
+            self.selected_lengths = self.lengths[sel.numpy()]
+            self._valid_lengths = None
         return sel
+
+    def peek_lengths(self, num_episodes):
+        """the lengths of the episodes the NEXT refresh_data(num_episodes) will select (host; nothing is selected); None for a dense file"""
+        if self.lengths is None:
+            return None
+        if num_episodes > self.num_recorded:
+            raise ValueError("{} holds {} episodes; {} were asked for".format(self.path, self.num_recorded, num_episodes))
+        return self.lengths[(np.arange(int(num_episodes)) + self._next) % self.num_recorded]
+
+    def _lengths_on_device(self):
+        """the selection's lengths as an int32 device tensor (N,): one upload per refresh"""
+        if self._valid_lengths is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+            self._valid_lengths = torch.from_numpy(self.selected_lengths.astype(np.int32)).to(dev)
+        return self._valid_lengths
+
+    def valid(self, t0, length):
+        """-> (length, N) uint8 device tensor, time-major like a chunk: 1 where timestep t0 + s of the n-th selected episode exists
+        (t0 + s < its length), 0 where it is padding; None for a dense file.  Built on the device from the lengths."""
+        if self.lengths is None:
+            return None
+        if self.selected_lengths is None:
+            raise ValueError("{}: refresh_data has not selected any episodes yet".format(type(self).__name__))
+        n = self._lengths_on_device()
+        steps = torch.arange(int(t0), int(t0) + int(length), dtype=torch.int32, device=n.device)
+        return (steps[:, None] < n[None, :]).to(torch.uint8)
 
     def _measure(self, x0, noise_scale):
         """a fresh measurement of the true poses x0, its noise drawn from the dataset's host generator"""
@@ -272,6 +354,8 @@ class RecordedEpisodeDataset(_TimestepItems):
         sel = self._select(num_episodes)
         data = {k: v[sel] for k, v in self.episodes.items()}
         data["measurement_self"] = self._measure(data["true_self"], noise_scale)
+        if self.lengths is not None:
+            data["lengths"] = torch.from_numpy(self.selected_lengths)
         self.data = data
 
 
@@ -289,6 +373,20 @@ def window_counts(num_episodes, horizon, sequence_length, stride):
     return per_episode, e * per_episode
 
 
+def ragged_window_counts(lengths, sequence_length, stride):
+    """(K_e per episode as a list, M): episode e of `lengths[e]` timesteps has K_e = (len_e - S) // stride + 1 windows of
+    `sequence_length` whose starts lie `stride` apart, none when it is shorter than a window"""
+    s, k = int(sequence_length), int(stride)
+    if k < 1:
+        raise ValueError("the window stride must be at least 1; got {!r}".format(stride))
+    if s < 1:
+        raise ValueError("a window needs at least 1 timestep; got {!r}".format(sequence_length))
+    per_episode = [(int(n) - s) // k + 1 if int(n) >= s else 0 for n in lengths]
+    if not per_episode:
+        raise ValueError("no episodes are selected")
+    return per_episode, sum(per_episode)
+
+
 class ResidentEpisodeDataset(RecordedEpisodeDataset):
     """RecordedEpisodeDataset with the whole file resident in device memory: same file format, same constructor plus `device`, same
     `refresh_data` -- the next `num_episodes` episodes in file order, wrapping, with measurement noise from the same host generator, so
@@ -297,7 +395,8 @@ class ResidentEpisodeDataset(RecordedEpisodeDataset):
     measurement pool is laid out like the others, (E_file, T, 7): one (episode, timestep) index addresses every array.
     `chunk(t0, S)` is the lockstep batch the parent would have staged, gathered on the device (rpe_gather_rows), which train() and
     evaluate_episodes prefer; `sampler(...)` draws shuffled minibatches of any size (WindowSampler).  `__getitem__` returns device
-    tensors."""
+    tensors.  A file with `lengths` has them uploaded once as well (`lengths_dev`, int32, one entry per episode in the file): the
+    sampler's launch and `valid` read them through `sel`, so both follow a refresh without a copy."""
 
     def __init__(self, path, use_depth=False, obj_name=None, seed=1234, device="cuda"):
         super().__init__(path, use_depth=use_depth, obj_name=obj_name, seed=seed)
@@ -307,6 +406,7 @@ class ResidentEpisodeDataset(RecordedEpisodeDataset):
         self.pool["measurement_self"] = self.pool["true_self"].clone()   # only the selected episodes' rows are ever read
         self.episodes = None                                  # (the host copy of the pixels is not kept)
         self.sel = torch.zeros(self.num_recorded, dtype=torch.int32, device=self.device)   # the first num_selected entries count
+        self.lengths_dev = None if self.lengths is None else torch.from_numpy(self.lengths.astype(np.int32)).to(self.device)
         self.num_selected = 0
         self.selected = []
 
@@ -320,6 +420,11 @@ class ResidentEpisodeDataset(RecordedEpisodeDataset):
         self.sel[:num_episodes].copy_(sel_dev.to(torch.int32))                      # in place: captured launches read these buffers
         self.pool["measurement_self"].index_copy_(0, sel_dev, meas.to(self.device))
         self.num_selected = int(num_episodes)
+        if self.lengths is not None:
+            self.data = {"lengths": torch.from_numpy(self.selected_lengths)}
+
+    def _lengths_on_device(self):
+        return self.lengths_dev[self.sel[:self.num_selected].long()]
 
     def _need_refresh(self):
         if self.num_selected < 1:
@@ -416,6 +521,10 @@ class WindowSampler(_DeviceStepCounter):
     a call replayed from a captured graph.  A call returns the six-tuple (img, depth, x0bar, x0, x1, obj), time-major (S, N, ...),
     in buffers the sampler owns: the next call overwrites them, and a captured consumer keeps their addresses.  refresh_data between
     calls changes the episodes and measurements the next call reads (the same number of episodes must stay selected).
+    A dataset with `lengths` (episodes of unequal length) goes through rpe_sample_windows_ragged: the window table is built on the
+    device at every launch from the lengths of whatever is selected, a window never reaches into padding, and an episode shorter than
+    a window is never drawn.  `windows_per_episode` is a list there; it, `num_windows` and `steps_per_epoch` follow the current
+    selection (host lengths), and a selection with fewer windows than a batch is a ValueError at the next call.
 
         sampler = dataset.sampler(256, shuffle=True, seed=0)
         for _ in range(sampler.steps_per_epoch):
@@ -432,14 +541,43 @@ class WindowSampler(_DeviceStepCounter):
         if self.batch_size < 1:
             raise ValueError("batch_size must be at least 1; got {!r}".format(batch_size))
         self.num_episodes = dataset.num_selected
-        self.windows_per_episode, self.num_windows = window_counts(self.num_episodes, dataset.env.horizon, self.sequence_length, self.stride)
-        if self.num_windows < self.batch_size:
-            raise ValueError("a batch of {} windows needs at least as many windows; {} episodes of {} timesteps give {} (sequence_length {}, stride {})".format(
-                self.batch_size, self.num_episodes, dataset.env.horizon, self.num_windows, self.sequence_length, self.stride))
-        self.steps_per_epoch = self.num_windows // self.batch_size
+        self.ragged = dataset.lengths is not None
+        self._counted = None        # (the selection counted, its (windows per episode, windows))
+        self.check_windows()
         dev = dataset.device
         self.index = torch.zeros(1 + 2 * self.batch_size, dtype=torch.int32, device=dev)   # [0] the step used, then (episode, t0) per window
         self._state = torch.zeros(1, dtype=torch.int32, device=dev)                         # the counter: on the dataset's device at once
+
+    def _counts(self):
+        """(windows per episode, windows) of the current selection: K and M = E K, or on a ragged dataset the list of K_e and their sum"""
+        ds = self.dataset
+        if not self.ragged:
+            if self._counted is None:   # E and T do not change: once
+                self._counted = (None, window_counts(self.num_episodes, ds.env.horizon, self.sequence_length, self.stride))
+        elif self._counted is None or self._counted[0] is not ds.selected_lengths:   # (refresh_data makes a new array)
+            if not 1 <= self.sequence_length <= ds.env.horizon:
+                raise ValueError("a window of {} timesteps does not fit episodes of {}".format(self.sequence_length, ds.env.horizon))
+            self._counted = (ds.selected_lengths, ragged_window_counts(ds.selected_lengths, self.sequence_length, self.stride))
+        return self._counted[1]
+
+    @property
+    def windows_per_episode(self):
+        return self._counts()[0]
+
+    @property
+    def num_windows(self):
+        return self._counts()[1]
+
+    @property
+    def steps_per_epoch(self):
+        return self.num_windows // self.batch_size
+
+    def check_windows(self):
+        """ValueError when the current selection holds fewer windows than a batch"""
+        if self.num_windows < self.batch_size:
+            raise ValueError("a batch of {} windows needs at least as many windows; {} episodes of {} timesteps give {} (sequence_length {}, stride {})".format(
+                self.batch_size, self.num_episodes, "up to {}".format(self.dataset.env.horizon) if self.ragged else self.dataset.env.horizon,
+                self.num_windows, self.sequence_length, self.stride))
 
     def desc_fields(self):
         """the integers of rpe_sample_desc"""
@@ -458,7 +596,11 @@ class WindowSampler(_DeviceStepCounter):
         ds = self.dataset
         if ds.num_selected != self.num_episodes:
             raise ValueError("the sampler was made for {} selected episodes; refresh_data has selected {} since".format(self.num_episodes, ds.num_selected))
-        ops.sample_windows(ops.sample_desc(**self.desc_fields()), ds.sel, self._state, out=self.index)
+        if self.ragged:
+            self.check_windows()   # the selection may have changed
+            ops.sample_windows_ragged(ops.sample_desc(**self.desc_fields()), ds.sel, ds.lengths_dev, self._state, out=self.index)
+        else:
+            ops.sample_windows(ops.sample_desc(**self.desc_fields()), ds.sel, self._state, out=self.index)
         return ds._batch(self.index, self.sequence_length, out=self.buffers())
 
 

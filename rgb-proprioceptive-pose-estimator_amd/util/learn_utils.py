@@ -25,7 +25,7 @@ import torch
 import torch.distributed as dist
 
 from ..dist import GradSync, broadcast_parameters, shard_bounds
-from .data_utils import FramePrefetcher, TrainInputs, model_batch, noisy_measurement, window_counts
+from .data_utils import FramePrefetcher, TrainInputs, model_batch, noisy_measurement, ragged_window_counts, window_counts
 
 
 def _writer(logging):
@@ -78,20 +78,23 @@ def sampled_steps_per_epoch(num_episodes, world, horizon, sequence_length, strid
     return min(steps)
 
 
-def train_step(model, batch, criterion, optimizer, train_obj_pose, phase="train", grad_sync=None):
+def train_step(model, batch, criterion, optimizer, train_obj_pose, phase="train", grad_sync=None, valid=None):
     """One iteration of the reference's hot loop (util/learn_utils.py:152-184).  Returns device scalars
-    (loss, pos_err, ori_err) -- nothing is synchronised to the host."""
+    (loss, pos_err, ori_err) -- nothing is synchronised to the host.
+    valid (dataset.valid(t0, S) of episodes of unequal length; None: every sample counts): the mask of the samples that exist, of
+    the outputs' leading shape; every criterion sums over those only."""
     img, depth, x0bar, x0, x1, obj = batch
+    masked = {} if valid is None else {"valid": valid}   # (None: the criteria are called exactly as before)
     optimizer.zero_grad()
     with torch.set_grad_enabled(phase == "train"):
         if train_obj_pose:
             obj_out = model(img, depth, x0bar)
-            loss = criterion["obj_loss"](obj_out, obj)
-            pos_err, ori_err = criterion["val_loss"].forward_device(obj_out, obj)
+            loss = criterion["obj_loss"](obj_out, obj, **masked)
+            pos_err, ori_err = criterion["val_loss"].forward_device(obj_out, obj, **masked)
         else:
             x0_out, x1_out = model(img, depth, x0bar)
-            loss = criterion["x0_loss"](x0_out, x0) + criterion["x1_loss"](x1_out, x1)
-            pos_err, ori_err = criterion["val_loss"].forward_device(x1_out, x1)
+            loss = criterion["x0_loss"](x0_out, x0, **masked) + criterion["x1_loss"](x1_out, x1, **masked)
+            pos_err, ori_err = criterion["val_loss"].forward_device(x1_out, x1, **masked)
         if phase == "train":
             loss.backward()
             if grad_sync is not None:
@@ -272,9 +275,11 @@ class EpisodeEvaluation:
     and host numbers (numpy float64; scalars, or (K,) in a sweep) read back in one transfer:
         pos_mean pos_std pos_max ori_mean ori_std ori_max, and per episode (E,) / (K, E): pos_episode_sum pos_episode_mean
         ori_episode_sum ori_episode_mean.
-    `stats` is the raw table they are views of: (K, 2, 3 + 2 E) = [scale][pos | ori][rpe_error_stats layout]."""
+    `stats` is the raw table they are views of: (K, 2, 3 + 2 E) = [scale][pos | ori][rpe_error_stats layout].
+    lengths: None, or for episodes of unequal length the numpy (E,) numbers of timesteps; every per-step entry at t >= lengths[e] is
+    NaN and the host numbers run over the timesteps that exist (rpe_error_stats_ragged)."""
 
-    def __init__(self, outputs, poses, pos_err, ori_err, stats, noise_scales=None, truth=None, measurements=None):
+    def __init__(self, outputs, poses, pos_err, ori_err, stats, noise_scales=None, truth=None, measurements=None, lengths=None):
         stats = np.asarray(stats, dtype=np.float64)
         self.noise_scales = None if noise_scales is None else [float(s) for s in noise_scales]
         k = 1 if noise_scales is None else len(self.noise_scales)
@@ -283,6 +288,7 @@ class EpisodeEvaluation:
             raise ValueError("stats must be (K, 2, 3 + 2 E); got %r for K = %d" % (stats.shape, k))
         self.outputs, self.poses, self.pos_err, self.ori_err, self.stats = outputs, poses, pos_err, ori_err, stats
         self.truth, self.measurements = truth, measurements
+        self.lengths = None if lengths is None else np.asarray(lengths)
         pick = (lambda a: a[0]) if noise_scales is None else (lambda a: a)
         for i, name in enumerate(("pos", "ori")):
             setattr(self, name + "_mean", pick(stats[:, i, 0]))
@@ -333,6 +339,10 @@ def evaluate_episodes(model, dataset, num_episodes, params, *, max_frames=256, n
     noise_scales=[s_0 .. s_{K-1}]: the same frames scored under K measurement-noise scales -- the trunk runs ONCE per chunk, the heads
     run with K E lanes on the feature rows repeated K times and measurements `sweep_measurements(x0, scales, z)` with
     z = sweep_draw(E, T, noise_seed); every field of the result gains a leading K dimension.
+    Episodes of unequal length (a dataset with `lengths`): all E lanes still advance over the padded horizon together -- a lane's output
+    depends on its own frames only, and on earlier ones through the LSTM, so what a finished lane computes from padding reaches nothing
+    that exists.  After the last chunk the per-step entries at t >= len_e are set to NaN (outputs, poses, pos_err, ori_err,
+    measurements, truth), the statistics come from rpe_error_stats_ragged over the timesteps that exist, and the result has `lengths`.
     Single process, device only (no CPU fallback).  model.training / model.rollout are restored and the carried state is reset."""
     from .. import ops
     if dist.is_initialized() and dist.get_world_size() > 1:
@@ -397,7 +407,16 @@ def evaluate_episodes(model, dataset, num_episodes, params, *, max_frames=256, n
                     outputs[:, :, t0:t0 + s].copy_(out)
                 t0 += s
             pos, ori, poses = ops.pose_errors(outputs, truth.unsqueeze(0).expand(K, E, T, 7).contiguous(), 1e-4, want_pose=True)
-            stats = torch.stack([torch.stack([ops.error_stats(pos[k]), ops.error_stats(ori[k])]) for k in range(K)])
+            lengths, n = getattr(dataset, "selected_lengths", None), None
+            if lengths is not None:   # episodes of unequal length: padding becomes NaN, and the statistics never read it
+                n = torch.from_numpy(lengths.astype(np.int32)).to(dev)
+                pad = torch.arange(T, dtype=torch.int32, device=dev)[None, :] >= n[:, None]   # (E, T)
+                for a in (pos, ori):
+                    a.masked_fill_(pad, float("nan"))
+                for a in (outputs, poses, meas):
+                    a.masked_fill_(pad[None, :, :, None], float("nan"))
+                truth.masked_fill_(pad[:, :, None], float("nan"))
+            stats = torch.stack([torch.stack([ops.error_stats(pos[k], n), ops.error_stats(ori[k], n)]) for k in range(K)])
             stats = stats.cpu().numpy()   # the one device -> host read of the evaluation
     finally:
         model.train(was_training)
@@ -407,7 +426,7 @@ def evaluate_episodes(model, dataset, num_episodes, params, *, max_frames=256, n
         model.reset_initial_state(E)
     if scales is None:
         outputs, poses, pos, ori, meas = outputs[0], poses[0], pos[0], ori[0], meas[0]
-    return EpisodeEvaluation(outputs, poses, pos, ori, stats, scales, truth=truth, measurements=meas)
+    return EpisodeEvaluation(outputs, poses, pos, ori, stats, scales, truth=truth, measurements=meas, lengths=lengths)
 
 
 # ---- rollout video: the estimate and the truth drawn on the recorded frames ------------------------------------------------------
@@ -528,9 +547,11 @@ def render_episodes(evaluation, frames, camera, *, draw=("truth", "estimate"), a
     return out
 
 
-def write_video(frames, path, fps=10):
+def write_video(frames, path, fps=10, lengths=None):
     """Write uint8 frames (..., Hs, Ws, 3) -- all leading dimensions are the frames in order, as render_episodes returns them -- to
-    `path`: `.npy` holds the raw (N, Hs, Ws, 3) array, `.gif` an animation at `fps` frames a second (Pillow)."""
+    `path`: `.npy` holds the raw (N, Hs, Ws, 3) array, `.gif` an animation at `fps` frames a second (Pillow).
+    lengths (E,): the frames are (E, T, Hs, Ws, 3) and episode e has lengths[e] of them; frames [lengths[e], T) are padding and are
+    dropped before writing."""
     ext = os.path.splitext(str(path))[1].lower()
     if ext not in (".npy", ".gif"):
         raise ValueError("write_video writes .npy (the raw array) or .gif; got {!r}".format(path))
@@ -539,6 +560,12 @@ def write_video(frames, path, fps=10):
     arr = frames.detach().cpu().numpy() if isinstance(frames, torch.Tensor) else np.asarray(frames)
     if arr.dtype != np.uint8 or arr.ndim < 4 or arr.shape[-1] != 3 or arr.size == 0:
         raise ValueError("frames must be uint8 (..., Hs, Ws, 3); got {} {}".format(arr.dtype, arr.shape))
+    if lengths is not None:
+        n = np.asarray(lengths.cpu() if isinstance(lengths, torch.Tensor) else lengths)
+        if arr.ndim != 5 or n.shape != arr.shape[:1] or n.dtype.kind not in "iu" or (n < 0).any() or (n > arr.shape[1]).any() or n.sum() == 0:
+            raise ValueError("write_video(lengths=...) takes frames (E, T, Hs, Ws, 3) and E integers in [0, T], not all 0; got frames {} and lengths {}".format(
+                arr.shape, n.tolist() if n.ndim == 1 and n.size <= 16 else n.shape))
+        arr = np.concatenate([arr[e, :int(k)] for e, k in enumerate(n)], 0)
     arr = np.ascontiguousarray(arr.reshape((-1,) + arr.shape[-3:]))
     if ext == ".npy":
         with open(path, "wb") as f:
@@ -618,7 +645,12 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
     per-tensor table of the last measured step is read WITH the phase's one host read (no synchronisation per step is added) and
     written as Telemetry/grad_norm/<name>, Telemetry/update_ratio/<name>, Telemetry/zero_frac/<name>; when a tensor has seen
     non-finite values, one line names the first one and its step.  telemetry_log: a list that receives every epoch's
-    telemetry_report(...).  The `val` phase is untouched."""
+    telemetry_report(...).  The `val` phase is untouched.
+    A dataset of episodes of unequal length (a file with `lengths`): the `val` phase walks the padded horizon in lockstep as ever, gives
+    every criterion dataset.valid(t0, S) and divides the epoch sums by the number of timesteps that exist; the `train` phase needs
+    batch_size, the device sampler, which never draws padding (the lockstep walk would feed padded frames into the batch statistics of
+    train-mode BatchNorm: a ValueError), and takes num_windows // batch_size steps of the current selection.  Under a process group
+    such a dataset is a ValueError: the shards' window counts can no longer be computed without communication."""
     if telemetry is not None and getattr(optimizer, "telemetry", None) != telemetry:
         raise ValueError("train(telemetry={!r}) needs an optimizer built with the same option (optim.FusedAdam(..., telemetry={!r})); got {} with telemetry={!r}".format(
             telemetry, telemetry, type(optimizer).__name__, getattr(optimizer, "telemetry", None)))
@@ -631,6 +663,19 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
                          "{} has none".format(type(dataset).__name__))
     if batch_size is None and (window_stride is not None or shuffle_seed != 0):
         raise ValueError("train(window_stride=..., shuffle_seed=...) belong to batch_size=...; without it the episodes are walked in lockstep")
+    ragged = getattr(dataset, "lengths", None) is not None
+    if ragged and batch_size is None:
+        raise ValueError("episodes of unequal length train from shuffled minibatches only: give train(batch_size=...) with a ResidentEpisodeDataset "
+                         "(scripts/train_model.py --resident --batch_size B); the lockstep walk would feed padded frames into BatchNorm's batch statistics")
+    if ragged and dist.is_initialized() and dist.get_world_size() > 1:
+        raise ValueError("episodes of unequal length under a process group are not built: the ranks' shards hold different numbers of windows, "
+                         "so the common step count cannot be computed without communication")
+    if ragged:   # the first `train` selection is known already: refuse a batch it cannot fill here, before the device is touched
+        s0 = model.sequence_length if model.requires_sequence else 1
+        m0 = ragged_window_counts(dataset.peek_lengths(num_train_episodes_per_epoch), s0, s0 if window_stride is None else window_stride)[1]
+        if m0 < int(batch_size):
+            raise ValueError("a batch of {} windows needs at least as many windows; the {} episodes of the first train phase hold {} "
+                             "(sequence_length {}, stride {})".format(batch_size, num_train_episodes_per_epoch, m0, s0, s0 if window_stride is None else window_stride))
     train_obj_pose = hasattr(model, "object_name")
     dt_string = datetime.now().strftime("%d-%m-%Y_%H-%M-%S")
     since = time.time()
@@ -675,18 +720,26 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
             if sampled:
                 if inputs.sampler is None:   # made after the first `train` refresh: it reads the number of selected episodes
                     inputs.draw_from(dataset.sampler(batch_size, sequence_length=seq, stride=window_stride, shuffle=True, seed=shuffle_seed + rank))
-                steps = sampled_steps_per_epoch(num_episodes, world, horizon, seq, inputs.sampler.stride, batch_size)
+                if ragged:   # (single process) the windows of THIS selection; fewer than a batch is the sampler's ValueError
+                    inputs.sampler.check_windows()
+                    steps = inputs.sampler.steps_per_epoch
+                else:
+                    steps = sampled_steps_per_epoch(num_episodes, world, horizon, seq, inputs.sampler.stride, batch_size)
                 if steps < 1:
                     raise ValueError("the smallest shard of {} episodes over {} ranks has fewer than batch_size = {} windows".format(num_episodes, world, batch_size))
                 model.reset_initial_state(batch_size)
                 batches = (None for _ in range(steps))   # `inputs` draws them
             else:
                 batches = (model_batch(b, model.requires_sequence) for b in _chunks(dataset, horizon, seq, getattr(model, "use_depth", False)))
+            masks = None   # episodes of unequal length, walked in lockstep (`val`): which samples of every chunk exist
+            if ragged and not sampled:
+                masks = (model_batch((dataset.valid(t0, min(seq, horizon - t0)),), model.requires_sequence)[0] for t0 in range(0, horizon, seq))
             with optimizer.averaged_weights(model) if phase == "val" and has_ema else contextlib.nullcontext():   # validate the average
                 for batch in batches:
                     if phase == "train":   # new tensors: what the dataset handed out is not written
                         batch = inputs(batch)
-                    loss, pe, oe = train_step(model, batch, criterion, optimizer, train_obj_pose, phase, grad_sync)
+                    loss, pe, oe = train_step(model, batch, criterion, optimizer, train_obj_pose, phase, grad_sync,
+                                              valid=None if masks is None else next(masks))
                     sums += torch.stack([loss.double(), pe.double(), oe.double()])
                     if clip_sums is not None:
                         clip_sums += torch.stack([optimizer.grad_norm.double(), (optimizer.clip_coef < 1.0).double()])
@@ -705,6 +758,8 @@ def train(model, dataset, criterion, optimizer, num_epochs, num_train_episodes_p
                 if measured:
                     tot, tele = tot[:n_head], telemetry_report(optimizer, model, tot[n_head:])
                 denom = steps * batch_size * seq * world if sampled else horizon * num_episodes
+                if masks is not None:   # the timesteps that exist
+                    denom = int(dataset.selected_lengths.sum())
                 epoch_loss, epoch_pos_err, epoch_ori_err = tot[0] / denom, tot[1] / denom, tot[2] / denom
                 if phase == "val" and has_ema and epoch_loss < best_err and save_model and rank == 0:
                     ema_sd = {k: v.detach().cpu().clone() for k, v in model.state_dict().items()}   # taken under the swap
