@@ -214,6 +214,9 @@ long rpe_x4_bytes(int dtype, int B, int H, int W);
 int rpe_stem_conv_fwd(int dtype, const void* x4, const void* w_packed, void* y, float* stats_part, int B, int H, int W, void* stream);
 int rpe_stem_conv_fwd_affine(int dtype, const void* x4, const void* w_packed, void* out, const float* bias, int relu, int B, int H, int W,
                              void* stream);
+/* dw_packed [64][8][8][4] fp32 += x4 (*) dy.  Atomic accumulation INTO what dw_packed holds: zero it first for the plain gradient.
+ * Channel 3 of every tap receives exactly 0 (x4's channel 3 is zero); tap row 7 / column 7 are not gradients (they meet the image
+ * shifted by one row / column) and rpe_unpack_stem_grad skips them. */
 int rpe_stem_conv_wgrad(int dtype, const void* x4, const void* dy, float* dw_packed, int B, int H, int W, void* stream);
 /* deterministic form (see rpe_conv2d_wgrad_det): dw_packed is overwritten */
 long rpe_stem_conv_wgrad_workspace_bytes(int dtype, int B, int H, int W);
@@ -243,7 +246,10 @@ int rpe_stage_image_nhwc4(int dtype, const float* img_nchw, void* out, int B, in
 
 /* replaces: the CPU image transform ToPILImage -> Resize(256) -> CenterCrop(224) -> ToTensor -> Normalize
  * (util/data_utils.py:48-54) for frames whose shorter side already equals the resize target: uint8 [B][Hs][Ws][3] frames are
- * centre-cropped to (H, W), normalised with the HOST arrays mean3/std3 and written as NHWC4 in the compute dtype. */
+ * centre-cropped to (H, W), normalised with the HOST arrays mean3/std3 and written as NHWC4 in the compute dtype.
+ * The crop starts at row (Hs - H) / 2, column (Ws - W) / 2 in integer division: an odd difference is FLOORED.  torchvision's CenterCrop
+ * rounds half to even there, so callers send odd differences to rpe_stage_frames_u8_resized with their own (top, left) instead
+ * (engine.py, ops.stage_frames); with both passes off that call is a pure window. */
 int rpe_stage_frames_u8(int dtype, const unsigned char* frames, void* out, int B, int Hs, int Ws, int H, int W, const float* mean3_host,
                         const float* std3_host, void* stream);
 /* The same for frames whose shorter side is not the transform's resize target: Pillow's antialiased 8-bit bilinear resample

@@ -37,6 +37,12 @@ class ConvDesc(Structure):
     _fields_ = [(n, c_int) for n in ("batch", "in_h", "in_w", "in_c", "out_c", "kh", "kw", "stride", "pad")]
 
 
+class PackDesc(Structure):
+    """rpe_pack_desc"""
+    _fields_ = [("src", c_void_p), ("wf", c_void_p), ("wd", c_void_p), ("Co", c_int), ("RS", c_int), ("Ci", c_int), ("pad_", c_int), ("start", c_long),
+                ("scale", c_void_p)]
+
+
 class AugmentDesc(Structure):
     """rpe_augment_desc"""
     _fields_ = ([("seed", ctypes.c_ulonglong)] + [(n, c_int) for n in ("qb_lo", "qb_hi", "qc_lo", "qc_hi", "qs_lo", "qs_hi", "noise_q")]

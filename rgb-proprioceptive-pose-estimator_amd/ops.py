@@ -350,9 +350,11 @@ def stage_image(img_nchw, dtype):
     return out
 
 
-def pack_stem_weight(w_oihw, dtype):
+def pack_stem_weight(w_oihw, dtype, scale=None):
+    """OIHW [64, 3, 7, 7] fp32 -> [64, 8, 8, 4] in `dtype` (tap row / column 7 and channel 3 zero); scale [64] fp32: w * scale[co] formed
+    in fp32 before the rounding (inference: BatchNorm folded into the conv)"""
     out = torch.empty((64, 8, 8, 4), dtype=dtype, device=w_oihw.device)
-    lib.rpe_pack_stem_weight(dtype_code(dtype), _p(_chk(w_oihw, "w")), None, _p(out), _stream())
+    lib.rpe_pack_stem_weight(dtype_code(dtype), _p(_chk(w_oihw, "w")), _p(scale), _p(out), _stream())
     return out
 
 
@@ -366,15 +368,48 @@ def stem_conv_fwd(x4, w_packed, want_stats=False):
     return (y, st) if want_stats else y
 
 
-def stem_conv_wgrad(x4, dy):
+def stem_conv_fwd_affine(x4, w_packed, bias, relu=True):
+    """Inference form of the stem: [relu](conv1(x4, w_packed) + bias) in one launch (w_packed = pack_stem_weight(w, dtype, scale))"""
+    b, h, w, _ = x4.shape
+    h, w = h - 2 * STEM_PAD, w - 2 * STEM_PAD
+    out = torch.empty((b, (h + 6 - 7) // 2 + 1, (w + 6 - 7) // 2 + 1, 64), dtype=x4.dtype, device=x4.device)
+    lib.rpe_stem_conv_fwd_affine(dtype_code(x4), _p(x4), _p(w_packed), _p(out), _p(bias), int(relu), b, h, w, _stream())
+    return out
+
+
+def stem_conv_wgrad(x4, dy, deterministic=True):
+    """-> dw OIHW [64, 3, 7, 7] fp32.  deterministic: per-workgroup tiles through the scratch buffer, summed in a fixed order
+    (rpe_stem_conv_wgrad_det); otherwise the atomic form the engine takes without a slab (it accumulates: dw_packed starts at zero)"""
     b, h, w, _ = x4.shape
     h, w = h - 2 * STEM_PAD, w - 2 * STEM_PAD
     dwp = torch.zeros((64, 8, 8, 4), dtype=torch.float32, device=x4.device)
-    ws = scratch(lib.rpe_stem_conv_wgrad_workspace_bytes(dtype_code(x4), b, h, w), x4.device)
-    lib.rpe_stem_conv_wgrad_det(dtype_code(x4), _p(x4), _p(dy), _p(dwp), b, h, w, _p(ws), ws.numel(), _stream())
+    if deterministic:
+        ws = scratch(lib.rpe_stem_conv_wgrad_workspace_bytes(dtype_code(x4), b, h, w), x4.device)
+        lib.rpe_stem_conv_wgrad_det(dtype_code(x4), _p(x4), _p(dy), _p(dwp), b, h, w, _p(ws), ws.numel(), _stream())
+    else:
+        lib.rpe_stem_conv_wgrad(dtype_code(x4), _p(x4), _p(dy), _p(dwp), b, h, w, _stream())
     dw = torch.empty((64, 3, 7, 7), dtype=torch.float32, device=x4.device)
     lib.rpe_unpack_stem_grad(_p(dwp), _p(dw), _stream())
     return dw
+
+
+def pack_conv_weights_multi(layers, dtype):
+    """Every layer of `layers` = [(w_krsc fp32 [Co, kh, kw, Ci], scale [Co] fp32 or None)] packed in ONE launch (rpe_pack_conv_weights_multi)
+    -> [(forward copy in `dtype`, scaled where a scale is given; dgrad copy [Ci, kh, kw, Co], unscaled)]"""
+    from ._lib import PackDesc
+    tab, outs, start = (PackDesc * len(layers))(), [], 0
+    for d, (w, scale) in zip(tab, layers):
+        co, kh, kw, ci = _chk(w, "w").shape
+        wf = torch.empty((co, kh, kw, ci), dtype=dtype, device=w.device)
+        wd = torch.empty((ci, kh, kw, co), dtype=dtype, device=w.device)
+        d.src, d.wf, d.wd, d.Co, d.RS, d.Ci, d.start = w.data_ptr(), wf.data_ptr(), wd.data_ptr(), co, kh * kw, ci, start
+        d.scale = None if scale is None else scale.data_ptr()
+        start += w.numel()
+        outs.append((wf, wd))
+    dev = layers[0][0].device
+    table = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+    lib.rpe_pack_conv_weights_multi(dtype_code(dtype), _p(table), len(layers), start, _stream())
+    return outs
 
 
 def bn_finalize(part, count, gamma, beta, running_mean=None, running_var=None, num_batches=None, momentum=0.1, eps=1e-5):
@@ -805,6 +840,76 @@ def stage_depth(raw, crop_hw=(224, 224), size=256):
         raise ValueError("frames of %dx%d resize to %dx%d, smaller than the %dx%d crop" % (hs, ws, hr, wr, h, w))
     top, left = crop_origin(hr, wr, h, w)
     return stage_depth_window(raw.contiguous(), hr, wr, top, left, h, w)
+
+
+_FRAME_TABLES = {}
+
+
+def _frame_tables(hs, ws, hr, wr, device):
+    """device tap tables of the Pillow-exact 8-bit resize for one frame geometry (built once, kept)"""
+    from .util.data_utils import pil_bilinear_tables
+    key = (hs, ws, hr, wr, device.type, device.index)
+    tabs = _FRAME_TABLES.get(key)
+    if tabs is None:
+        tabs = []
+        for i, o in ((ws, wr), (hs, hr)):
+            if i == o:
+                tabs.append((None, None, 0))
+            else:
+                bounds, kk = pil_bilinear_tables(i, o)
+                tabs.append((torch.from_numpy(bounds).to(device), torch.from_numpy(kk).contiguous().to(device), kk.shape[1]))
+        _FRAME_TABLES[key] = tabs
+    return tabs
+
+
+def _norm3(v):
+    return (ctypes.c_float * 3)(*(float(x) for x in v))
+
+
+def stage_frames_window(frames, dtype, hr, wr, top, left, h, w, mean, std):
+    """frames uint8 [B, Hs, Ws, 3] -> the zero-bordered NHWC4 image [B, h + 6, w + 6, 4] in `dtype`: the window [top, top + h) x
+    [left, left + w) of Pillow's 8-bit bilinear resize of every frame to hr x wr, normalised (rpe_stage_frames_u8_resized)."""
+    _chk(frames, "frames")
+    if frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
+        raise ValueError("stage_frames_window: frames must be uint8 [B, Hs, Ws, 3]; got %s %r" % (frames.dtype, tuple(frames.shape)))
+    b, hs, ws, _ = frames.shape
+    if top < 0 or left < 0 or top + h > hr or left + w > wr:
+        raise ValueError("stage_frames_window: the %dx%d window at (%d, %d) leaves the %dx%d resized frame" % (h, w, top, left, hr, wr))
+    (xb, xk, ksx), (yb, yk, ksy) = _frame_tables(hs, ws, hr, wr, frames.device)
+    tmp = torch.empty(b * hs * wr * 3, dtype=torch.uint8, device=frames.device) if xb is not None else None
+    out = torch.zeros((b, h + 2 * STEM_PAD, w + 2 * STEM_PAD, 4), dtype=dtype, device=frames.device)
+    lib.rpe_stage_frames_u8_resized(dtype_code(dtype), _p(frames), _p(out), b, hs, ws, hr, wr, top, left, h, w, _p(xb), _p(xk), ksx, _p(yb), _p(yk), ksy,
+                                    _p(tmp), _norm3(mean), _norm3(std), _stream())
+    return out
+
+
+def frames_route(hs, ws, h, w, size=256):
+    """How frames of hs x ws reach a crop of h x w, exactly as engine.py decides it: ("plain",) -- rpe_stage_frames_u8, only when nothing
+    is resized and both crop differences are even (the kernel floors its centre crop) -- or ("window", hr, wr, top, left) with
+    crop_origin's offsets (torchvision's CenterCrop rounds half to even)."""
+    from .util.data_utils import crop_origin, resized_hw
+    hr, wr = resized_hw(hs, ws, size)
+    if min(hr, wr) < min(h, w) or hr < h or wr < w:
+        raise ValueError("frames of %dx%d resize to %dx%d, smaller than the %dx%d crop" % (hs, ws, hr, wr, h, w))
+    if (hr, wr) == (hs, ws) and (hs - h) % 2 == 0 and (ws - w) % 2 == 0:
+        return ("plain",)
+    return ("window", hr, wr) + crop_origin(hr, wr, h, w)
+
+
+def stage_frames(frames, dtype, crop_hw=(224, 224), size=256, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225)):
+    """The reference's image transform (ToPILImage -> Resize(size) -> CenterCrop(crop_hw) -> ToTensor -> Normalize) on the device:
+    frames uint8 [B, Hs, Ws, 3] -> the zero-bordered NHWC4 image [B, H + 6, W + 6, 4] in `dtype`, routed as engine.py routes it."""
+    _chk(frames, "frames")
+    if frames.dim() != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
+        raise ValueError("stage_frames: frames must be uint8 [B, Hs, Ws, 3]; got %s %r" % (frames.dtype, tuple(frames.shape)))
+    b, hs, ws, _ = frames.shape
+    h, w = crop_hw
+    route = frames_route(hs, ws, h, w, size)
+    if route[0] == "plain":
+        out = torch.zeros((b, h + 2 * STEM_PAD, w + 2 * STEM_PAD, 4), dtype=dtype, device=frames.device)
+        lib.rpe_stage_frames_u8(dtype_code(dtype), _p(frames), _p(out), b, hs, ws, h, w, _norm3(mean), _norm3(std), _stream())
+        return out
+    return stage_frames_window(frames, dtype, *route[1:], h, w, mean, std)
 
 
 AUGMENT_DESC_FIELDS = ("seed", "qb_lo", "qb_hi", "qc_lo", "qc_hi", "qs_lo", "qs_hi", "noise_q", "erase_thresh", "eh_lo", "eh_hi", "ew_lo", "ew_hi",
