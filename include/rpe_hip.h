@@ -382,6 +382,30 @@ typedef struct {
 int rpe_augment_depth_f32(const float* in, float* out, int B, int Hs, int Ws, const rpe_depth_augment_desc* d, unsigned* state, int* params,
                           const int* rgb_params, int rgb_group, void* stream);
 
+/* replaces: the dropout the reference's sequence models promise and never apply ("dropout_prob ... TODO: Currently does nothing",
+ * models/time_sensitive.py): inverted dropout on the rows the heads read, the mask drawn on the device ("Head dropout").
+ * Element (r, c) of an fp32 [n][ld] matrix, c the ABSOLUTE column: words = Philox4x32-10 keyed by `seed` (low word, high word) at
+ * counter (r, c >> 2, step, 0x44524F50 + site); the element's word is number c & 3; kept iff word >= thresh.  kept: out = x * scale,
+ * one correctly rounded fp32 multiply; dropped: out = +0.0f by selection (a NaN or an infinity in a dropped position does not survive,
+ * -0 does not appear).  The host derives thresh = min(2^32 - 1, round(p 2^32)) and scale = (float)(1.0 / (1.0 - p)) for 0 <= p < 1;
+ * with p = 0 it launches nothing. */
+typedef struct {
+    unsigned long long seed;   /* Philox key: k0 = low word, k1 = high word */
+    unsigned thresh;           /* an element is dropped iff its word < thresh */
+    float scale;               /* what a kept element is multiplied by */
+} rpe_dropout_desc;
+/* state: device, state[0] is the step counter.  picks: device, one int.  The launch writes picks[0] = state[0] and advances the counter
+ * by one (wrapping at 2^32); it is the only reader and writer of `state`, so a captured train step draws a fresh mask at every
+ * replay.  Every rpe_dropout_rows_f32 launch of that step reads picks[0]: forward and backward agree whatever order they run in.
+ * One launch. */
+int rpe_dropout_begin(unsigned* state, int* picks, void* stream);
+/* x, out: device, fp32 [n][ld], the same buffer (in place) or disjoint ones.  Only columns [c0, c1) are read and written; everything
+ * else keeps its contents in either mode.  site 0..3 selects the purpose word, so sites draw unrelated masks in one step.  One thread
+ * per aligned group of four columns, rows grid-stride; 16-byte accesses when both pointers are 16-byte aligned and ld % 4 == 0,
+ * 4-byte ones for the partial groups at either end.  Refused: n < 1 or n >= 2^32, c0 < 0, c1 > ld, c0 >= c1, site outside 0..3,
+ * buffers that overlap without being equal.  One launch; serves activations (forward) and gradients (backward) alike. */
+int rpe_dropout_rows_f32(const float* x, float* out, long n, int ld, int c0, int c1, int site, const int* picks, const rpe_dropout_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ batch norm */
 /* replaces: nn.BatchNorm2d (train mode: biased batch variance, eps, momentum with
  * unbiased running variance) + the in-place nn.ReLU and `out += identity` of the

@@ -60,6 +60,11 @@ class MeasureDesc(Structure):
     _fields_ = [("seed", ctypes.c_ulonglong)] + [(n, c_int) for n in ("S", "N", "num_scales")] + [("sigma", c_double * 8), ("rho", c_double)]
 
 
+class DropoutDesc(Structure):
+    """rpe_dropout_desc"""
+    _fields_ = [("seed", ctypes.c_ulonglong), ("thresh", ctypes.c_uint), ("scale", c_float)]
+
+
 class DepthAugmentDesc(Structure):
     """rpe_depth_augment_desc"""
     _fields_ = ([("seed", ctypes.c_ulonglong)] + [(n, c_double) for n in ("n0", "n1", "n2", "q", "inv_q", "lo", "hi")] + [("drop_thresh", ctypes.c_uint)]
@@ -139,6 +144,8 @@ _SPEC = {
     "rpe_sample_windows_ragged": (I, [POINTER(SampleDesc), P, P, P, P, P]),
     "rpe_gather_rows": (I, [P, P, L, L, P, I, I, P]),
     "rpe_measurement_noise": (I, [P, P, POINTER(MeasureDesc), P, P, P]),
+    "rpe_dropout_begin": (I, [P, P, P]),
+    "rpe_dropout_rows_f32": (I, [P, P, L, I, I, I, I, P, POINTER(DropoutDesc), P]),
     "rpe_bn_finalize": (I, [P, I, I, L, P, P, P, P, P, F, F, P, P, P, P, P, P]),
     "rpe_bn_eval_affine": (I, [I, P, P, P, P, F, P, P, P]),
     "rpe_bn_apply": (I, [I, P, P, P, P, P, L, I, I, P]),

@@ -180,6 +180,13 @@ class PoseModelBase(nn.Module):
         self._aux_ops = None
         self._grad_sync = None   # dist.GradSync attached by the data-parallel loop (staged all-reduce under backward)
         self.rollout = False
+        # head dropout (set_dropout): off.  Plain attributes, not buffers: state_dict() keeps the reference's keys
+        self._drop_p = (0.0, 0.0)
+        self._drop_seed = 0
+        self._drop_desc = {}     # site -> rpe_dropout_desc of the sites that are on
+        self._drop_live = {}     # ... as the last forward that kept state for a backward used them: what that backward masks with
+        self._drop_state = None  # int32 [1] on the device: the step counter, advanced by the device alone
+        self._drop_picks = None  # int32 [1] on the device: the step of the current train step
 
     # -- helpers --------------------------------------------------------------------------------
     @property
@@ -193,6 +200,64 @@ class PoseModelBase(nn.Module):
             aux, dep = aux.module, dep.module
         return aux[0], dep[-2]  # Conv2d, InstanceNorm2d
 
+    # -- head dropout ---------------------------------------------------------------------------
+    HIDDEN_DROPOUT_SITES = ()   # the sites of the LSTM outputs a class has (the sequence classes name theirs)
+
+    def set_dropout(self, feature=0.0, hidden=0.0, seed=0):
+        """Inverted dropout on the rows the heads read, in training forwards only ("Head dropout"); returns the model.
+        feature: drop probability of the fused feature columns [0, latent_dim + aux_latent_dim) -- site 0; the proprioceptive
+            columns behind them are never dropped.
+        hidden: drop probability of every step's LSTM output h in front of the Linear that reads it -- sites 1 and 2; the LSTM's own
+            recurrence and the carried (h, c) see the undropped h.  The classes without an LSTM refuse hidden > 0.
+        seed: 64-bit key of the device generator.  The mask of an element depends on (seed, step, site, row, column) alone, the step
+            counter lives in device memory and moves once per training forward, so a captured train step draws a fresh mask at every
+            replay.  Data-parallel replicas must not share masks: give replica r the seed K + r (scripts/train_model.py does).
+        Both probabilities lie in [0, 1); 0 turns a site off, and with both 0 a step launches nothing for dropout.  Active only in a
+        forward that keeps state for a backward (train mode with grad enabled): eval(), no_grad, features_only / heads_only, rollout,
+        evaluation, capture and saliency never drop and never move the counter."""
+        feature, hidden, seed = float(feature), float(hidden), int(seed)
+        for name, p in (("feature", feature), ("hidden", hidden)):
+            if not 0.0 <= p < 1.0:
+                raise ValueError("set_dropout: %s must lie in [0, 1); got %r" % (name, p))
+        if not 0 <= seed < 2 ** 64:
+            raise ValueError("set_dropout: seed must fit 64 unsigned bits; got %r" % (seed,))
+        if hidden > 0.0 and not self.HIDDEN_DROPOUT_SITES:
+            raise ValueError("set_dropout: %s has no LSTM output to drop: it takes `feature` only; got hidden = %r" % (type(self).__name__, hidden))
+        desc = {}
+        if feature > 0.0:
+            desc[0] = ops.dropout_desc(feature, seed)
+        if hidden > 0.0:
+            for site in self.HIDDEN_DROPOUT_SITES:
+                desc[site] = ops.dropout_desc(hidden, seed)
+        desc = {k: d for k, d in desc.items() if d.thresh > 0}   # (a p that rounds to threshold 0 drops nothing and scales by 1)
+        self._drop_p, self._drop_seed, self._drop_desc = (feature, hidden), seed, desc
+        p0 = next(self.parameters(), None)
+        if p0 is not None and p0.is_cuda:
+            self._drop_alloc(p0.device)
+        return self
+
+    def _drop_alloc(self, device):
+        """the counter and the step word, once per model: never reallocated, so a captured graph stays valid"""
+        if self._drop_state is None:
+            self._drop_state = torch.zeros(1, dtype=torch.int32, device=device)
+            self._drop_picks = torch.zeros(1, dtype=torch.int32, device=device)
+        elif self._drop_state.device != device:
+            raise RuntimeError("the dropout state of this model lives on %s; the batch is on %s" % (self._drop_state.device, device))
+
+    def _drop_begin(self, save):
+        """At the top of a forward's head part: a forward that keeps state for a backward fixes the sites and their descriptors for
+        that backward and, when any is on, takes the step (one launch).  Any other forward leaves everything alone."""
+        if not save:
+            return
+        self._drop_live = dict(self._drop_desc)
+        if self._drop_live:
+            ops.dropout_begin(self._drop_state, self._drop_picks)
+
+    def _drop(self, site, x, out=None, c0=0, c1=None):
+        """The ONE route of every dropout launch, forward (activations) and backward (gradients): columns [c0, c1) of the row matrix
+        x through the mask of `site` at the step _drop_begin took; out=None: in place."""
+        return ops.dropout_rows(x, self._drop_live[site], self._drop_picks, site=site, c0=c0, c1=c1, out=out)
+
     def _materialize(self, device):
         """First call on a device: put every parameter into one flat arena and bind gradient views."""
         p0 = next(self.parameters())
@@ -200,6 +265,8 @@ class PoseModelBase(nn.Module):
             raise RuntimeError("model parameters are on %s but the batch is on %s: call model.cuda() first" % (p0.device, device))
         if device.type != "cuda":
             raise RuntimeError("the pose models run on the MI355X HIP path only; there is no CPU fallback (got %s tensors)" % device)
+        if self._drop_desc and self._drop_state is None:   # set_dropout was called while the model was still on the CPU
+            self._drop_alloc(device)
         self.trunk.compute_dtype = self.compute_dtype
         self.trunk.ensure_layout()
         if self._arena is None or not self._arena.is_current():
@@ -248,7 +315,11 @@ class PoseModelBase(nn.Module):
     def _forward_impl(self, img, depth, x0bar, save):
         """trunk + early-feature heads into the feature rows, then the model's own heads on those rows"""
         lead, img, depth, x0bar = self._flat_inputs(img, depth, x0bar)
-        return self._heads_fwd(self._feature_rows(img, depth, save), lead, x0bar, save)
+        rows = self._feature_rows(img, depth, save)
+        self._drop_begin(save)
+        if save and 0 in self._drop_live:   # site 0: the feature columns, in place; whatever lies behind them is not touched
+            self._drop(0, rows, c1=self.latent_dim + self.aux_latent_dim)
+        return self._heads_fwd(rows, lead, x0bar, save)
 
     def features_only(self, img, depth):
         """The measurement-independent half of an inference forward: (lead, rows) with lead = (S, N) or (N,) and rows the fused
@@ -298,6 +369,8 @@ class PoseModelBase(nn.Module):
 
     def _features_bwd(self, d_rows):
         """d_rows [B, ld >= L + aux] gradient of the fused feature rows."""
+        if 0 in self._drop_live:   # the forward dropped these columns: the same mask on their (summed) gradient, once, in place
+            self._drop(0, d_rows, c1=self.latent_dim + self.aux_latent_dim)
         use_early = self.aux_nets is not None and 9 in self._hooks   # (the bn1 hook's gradient enters the stem backward)
         if self.aux_nets is not None:
             off = self.latent_dim

@@ -1,7 +1,8 @@
 """LSTM (temporally dependent) pose regressors on the MI355X HIP path.
 
 Drop-in for models/time_sensitive.py of the reference: class names, constructor signatures
-(`dropout_prob` and `device` accepted and unused, as there), attributes (`sequence_length`,
+(`dropout_prob` and `device` accepted and unused, as there; dropout is switched on with
+`set_dropout`, off by default), attributes (`sequence_length`,
 `rollout`, `requires_sequence`, `reset_initial_state`), state_dict keys and return values are kept.
 Inputs are time-major (S, N, ...); all S*N frames go through the trunk as one batch
 (time_sensitive.py:181-182) and the LSTMs start from zeros each chunk unless `rollout` is set,
@@ -53,6 +54,19 @@ class _SequenceModel(PoseModelBase):
                 st[0].copy_(hc[0])
                 st[1].copy_(hc[1])
 
+    def _drop_h(self, site, h, save):
+        """every step's LSTM output h [S*N, H] in front of the Linear that reads it: dropped OUT of place when `site` is on in this
+        forward (the LSTM keeps its own h for its backward, and the carried (h, c) is never dropped), h itself otherwise"""
+        if not (save and site in self._drop_live):
+            return h
+        return self._drop(site, h, out=torch.empty_like(h))
+
+    def _drop_dh(self, site, dh):
+        """the gradient of that dropped h, masked in place in front of LSTMOp.bwd"""
+        if site in self._drop_live:
+            self._drop(site, dh)
+        return dh
+
     def _reset_carried(self):
         """zero initial state (reset_initial_state of the reference: time_sensitive.py:256-270,519-529,788-800), in place"""
         for h, c in self._carried.values():
@@ -68,6 +82,8 @@ class TemporallyDependentStateEstimator(_SequenceModel):
     """Two-arm model: features -> LSTM -> Linear = own eef pose; (pose - measurement) joined to the features
     -> LSTM -> Linear = other arm's pose.  reference: models/time_sensitive.py:8-274 (forward :165-254).
     Quirk kept: the aux/depth heads live in plain lists, so they are neither trained nor saved."""
+
+    HIDDEN_DROPOUT_SITES = (1, 2)   # the pre- and the post-measurement LSTM
 
     def __init__(self, hidden_dim_pre_measurement, hidden_dim_post_measurement, num_resnet_layers=50, latent_dim=50,
                  sequence_length=10, dropout_prob=0.10, feature_extract=True, feature_layer_nums=(9,), use_depth=False,
@@ -106,14 +122,14 @@ class TemporallyDependentStateEstimator(_SequenceModel):
         h0, c0 = self._state("pre", N, self.pre_measurement_hidden_dim, dev)
         hp, hc = self._pre_rnn.fwd(rows, S, N, h0, c0, save=save)
         self._keep("pre", hc)
-        pre = self._pre_fc.fwd(hp, save=save)
+        pre = self._pre_fc.fwd(self._drop_h(1, hp, save), save=save)
         post_in = new_rows(S * N, F + 7, dev)
         ops.copy2d(rows, post_in, cols=F)
         ops.copy2d((pre - x0bar).contiguous(), post_in[:, F:], cols=7)
         h0, c0 = self._state("post", N, self.post_measurement_hidden_dim, dev)
         hq, hc = self._post_rnn.fwd(post_in, S, N, h0, c0, save=save)
         self._keep("post", hc)
-        post = self._post_fc.fwd(hq, save=save)
+        post = self._post_fc.fwd(self._drop_h(2, hq, save), save=save)
         self._sn = (S, N)
         return pre.contiguous().view(S, N, 7), post.contiguous().view(S, N, 7)
 
@@ -124,14 +140,14 @@ class TemporallyDependentStateEstimator(_SequenceModel):
         dev = self._pre_fc.x.device
         d = self._pad_rows(d_post, 7) if d_post is not None else new_rows(S * N, 7, dev)
         d = self._post_fc.bwd(d)
-        d = self._post_rnn.bwd(d)  # [S*N, F+7]
+        d = self._post_rnn.bwd(self._drop_dh(2, d))  # [S*N, F+7]
         d_rows = new_rows(S * N, F, dev)
         ops.copy2d(d, d_rows, cols=F)
         d_pre_total = d[:, F:F + 7].contiguous()
         if d_pre is not None:
             d_pre_total = d_pre_total + d_pre.reshape(S * N, 7)
         d = self._pre_fc.bwd(self._pad_rows(d_pre_total, 7))
-        d = self._pre_rnn.bwd(d)
+        d = self._pre_rnn.bwd(self._drop_dh(1, d))
         d_rows.add_(d)
         self._features_bwd(d_rows)
 
@@ -145,6 +161,8 @@ class TemporallyDependentStateEstimator(_SequenceModel):
 class TemporallyDependentObjectStateEstimator(_SequenceModel):
     """features (+aux, +proprioception) -> LSTM -> Linear(h, h/4) -> Linear(h/4, 7), no activation between.
     reference: models/time_sensitive.py:277-533 (forward :453-517)."""
+
+    HIDDEN_DROPOUT_SITES = (1,)
 
     def __init__(self, object_name, hidden_dim, num_resnet_layers=50, latent_dim=50, sequence_length=10, dropout_prob=0.10,
                  feature_extract=True, feature_layer_nums=(9,), use_depth=False, use_pretrained=True, no_proprioception=False,
@@ -183,14 +201,14 @@ class TemporallyDependentObjectStateEstimator(_SequenceModel):
         h0, c0 = self._state("rnn", N, self.hidden_dim, dev)
         h, hc = self._rnn.fwd(rows, S, N, h0, c0, save=save)
         self._keep("rnn", hc)
-        out = self._fc1.fwd(self._fc0.fwd(h, save=save), save=save)
+        out = self._fc1.fwd(self._fc0.fwd(self._drop_h(1, h, save), save=save), save=save)
         self._sn = (S, N)
         return (out.contiguous().view(S, N, 7),)
 
     def _backward_impl(self, d_outs):
         d = self._fc1.bwd(self._pad_rows(d_outs[0], 7))
         d = self._fc0.bwd(d)
-        d = self._rnn.bwd(d)
+        d = self._rnn.bwd(self._drop_dh(1, d))
         self._features_bwd(d)
 
     def reset_initial_state(self, batch_size):
@@ -202,6 +220,8 @@ class TemporallyDependentObjectStateEstimator(_SequenceModel):
 class TemporallyDependentObjectStateEstimatorV2(_SequenceModel):
     """Separate LSTMs per modality (image features / proprioception), concatenated into a 2-layer FC.
     reference: models/time_sensitive.py:536-804 (forward :714-786)."""
+
+    HIDDEN_DROPOUT_SITES = (1, 2)   # the image and the proprioceptive LSTM
 
     def __init__(self, object_name, img_hidden_dim, proprio_hidden_dim=64, num_resnet_layers=50, latent_dim=50, sequence_length=10,
                  dropout_prob=0.10, feature_extract=True, feature_layer_nums=(9,), use_depth=False, use_pretrained=True, device='cpu',
@@ -246,8 +266,8 @@ class TemporallyDependentObjectStateEstimatorV2(_SequenceModel):
         hp, hc = self._prop_rnn.fwd(prop, S, N, h0, c0, save=save)
         self._keep("proprio", hc)
         cat = new_rows(S * N, Hi + Hp, dev)
-        ops.copy2d(hi, cat, cols=Hi)
-        ops.copy2d(hp, cat[:, Hi:], cols=Hp)
+        ops.copy2d(self._drop_h(1, hi, save), cat, cols=Hi)
+        ops.copy2d(self._drop_h(2, hp, save), cat[:, Hi:], cols=Hp)
         out = self._fc1.fwd(self._fc0.fwd(cat, save=save), save=save)
         self._sn = (S, N)
         return (out.contiguous().view(S, N, 7),)
@@ -258,8 +278,8 @@ class TemporallyDependentObjectStateEstimatorV2(_SequenceModel):
         d = self._fc0.bwd(d)  # [S*N, Hi+Hp]
         d_hi = d[:, :Hi].contiguous()
         d_hp = d[:, Hi:Hi + Hp].contiguous()
-        self._prop_rnn.bwd(d_hp, need_dx=False)
-        self._features_bwd(self._img_rnn.bwd(d_hi))
+        self._prop_rnn.bwd(self._drop_dh(2, d_hp), need_dx=False)
+        self._features_bwd(self._img_rnn.bwd(self._drop_dh(1, d_hi)))
 
     def reset_initial_state(self, batch_size):
         """Zero the carried LSTM states (reference: models/time_sensitive.py:788-800)."""

@@ -1411,3 +1411,67 @@ def measurement_noise(x0, desc, state, picks=None, out=None):
         raise ValueError("measurement_noise: picks must be int32 with at least %d elements on x0's device" % (1 + n))
     lib.rpe_measurement_noise(_p(x0), _p(out), ctypes.byref(desc), _p(_chk(state, "state")), _p(_chk(picks, "picks")), _stream())
     return out
+
+
+DROPOUT_SITES = 4
+
+
+def dropout_desc(p, seed=0):
+    """rpe_dropout_desc of drop probability p in [0, 1): thresh = min(2^32 - 1, round(p 2^32)) (the rule of the depth augmentation's
+    drop_thresh), scale = float32(1 / (1 - p)) divided in double and rounded once; seed: the 64-bit Philox key.  p = 0 gives thresh 0
+    and scale 1: nothing would be dropped, and callers launch nothing (PoseModelBase.set_dropout leaves such a site off)."""
+    from ._lib import DropoutDesc
+    p, seed = float(p), int(seed)
+    if not 0.0 <= p < 1.0:
+        raise ValueError("dropout_desc: p must lie in [0, 1); got %r" % (p,))
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError("dropout_desc: seed must fit 64 unsigned bits; got %r" % (seed,))
+    d = DropoutDesc()
+    d.seed, d.thresh, d.scale = seed, min(2 ** 32 - 1, int(round(p * 2 ** 32))), 1.0 / (1.0 - p)
+    return d
+
+
+def _dropout_word(t, dev, name):
+    """`state` / `picks` of the dropout entry points: a contiguous int32 tensor on the device `dev` (None: any GPU)"""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or t.numel() < 1 or not t.is_cuda or (dev is not None and t.device != dev):
+        raise ValueError("%s must be an int32 tensor on the device" % name)
+    return _chk(t, name)
+
+
+def dropout_begin(state, picks):
+    """picks[0] <- the step counter state[0], which then advances by one, wrapping at 2^32 (rpe_dropout_begin): once per train step,
+    in front of its dropout_rows launches.  state, picks: int32 device tensors (the counter's 32 bits are stored as they are)."""
+    _dropout_word(state, None, "dropout_begin: state")
+    _dropout_word(picks, state.device, "dropout_begin: picks")
+    lib.rpe_dropout_begin(_p(state), _p(picks), _stream())
+    return picks
+
+
+def dropout_rows(x, desc, picks, site=0, c0=0, c1=None, out=None):
+    """Inverted dropout of columns [c0, c1) of the fp32 row matrix x [n, cols] (any row stride; unit column stride), the mask of step
+    picks[0] and of `site` (0..3): kept elements are multiplied by desc.scale, dropped ones become +0.0 (rpe_dropout_rows_f32).
+    out: None or x itself = in place; otherwise a matrix of x's shape and row stride that shares no memory with it, of which only
+    the columns [c0, c1) are written.  The same call masks the gradient in the backward.  Returns out."""
+    if not isinstance(x, torch.Tensor) or x.dtype != torch.float32 or x.dim() != 2 or x.numel() == 0 or (x.shape[1] > 1 and x.stride(1) != 1):
+        raise ValueError("dropout_rows: x must be a non-empty fp32 matrix with unit column stride")
+    if not x.is_cuda:
+        raise ValueError("dropout_rows: x must be on the device (there is no CPU path)")
+    n, cols = x.shape
+    ld = x.stride(0) if n > 1 else max(x.stride(0), cols)
+    c1 = cols if c1 is None else int(c1)
+    c0, site = int(c0), int(site)
+    if not 0 <= c0 < c1 <= cols:
+        raise ValueError("dropout_rows: the columns must satisfy 0 <= c0 < c1 <= %d; got [%d, %d)" % (cols, c0, c1))
+    if not 0 <= site < DROPOUT_SITES:
+        raise ValueError("dropout_rows: site must lie in [0, %d); got %r" % (DROPOUT_SITES, site))
+    if ld < cols or ld >= 2 ** 31:
+        raise ValueError("dropout_rows: the row stride must be at least the column count (rows may not overlap); got %d for %d columns" % (ld, cols))
+    _dropout_word(picks, x.device, "dropout_rows: picks")
+    if out is None:
+        out = x
+    elif out is not x:
+        if not isinstance(out, torch.Tensor) or out.dtype != torch.float32 or tuple(out.shape) != (n, cols) or out.device != x.device \
+                or (n > 1 and out.stride(0) != ld) or (cols > 1 and out.stride(1) != 1):
+            raise ValueError("dropout_rows: out must be fp32 of x's shape and row stride on its device")
+    lib.rpe_dropout_rows_f32(_p(x), _p(out), n, ld, c0, c1, site, _p(picks), ctypes.byref(desc), _stream())
+    return out

@@ -23,6 +23,8 @@ ResNet; models/losses.py:114-128 is the loss; util/learn_utils.py:152-184 the st
     rpe::sample_windows_ragged / pose_loss_masked / (no counterpart: the reference's episodes all have one length) the window index, the summed loss and the
     rpe::error_stats_ragged                         error statistics of episodes of unequal length, padded to one horizon: padding is never drawn or read
     rpe::measurement_noise                          x0 + sqrt(scale) * randn_like(x0) with the quaternion renormalised (util/data_utils.py:162-167), drawn on the device
+    rpe::dropout_begin / dropout_rows               F.dropout on a column range of the rows the heads read (the `dropout_prob` the reference accepts and never applies),
+                                                    the mask drawn on the device from a step counter in device memory
     rpe::occlude_grid_u8 / pose_displacement /      (no counterpart: occlusion sensitivity) a frame with one rectangle of a grid covered per row; how far
     rpe::saliency_map / saliency_overlay_u8         each prediction moved; the scores spread over the pixels; the map drawn over the frame
     rpe::project_poses / draw_poses_u8              the recorded video of rollout() (util/learn_utils.py:401-403, 462-504) without the simulator: poses through a camera
@@ -39,7 +41,7 @@ __all__ = ["NAMES"]
 
 _NS = "rpe"
 NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step", "augment_frames_u8", "augment_depth_f32", "sample_windows", "gather_rows",
-         "sample_windows_ragged", "pose_loss_masked", "error_stats_ragged", "measurement_noise", "occlude_grid_u8", "pose_displacement", "saliency_map", "saliency_overlay_u8", "param_stats", "project_poses", "draw_poses_u8")
+         "sample_windows_ragged", "pose_loss_masked", "error_stats_ragged", "measurement_noise", "occlude_grid_u8", "pose_displacement", "saliency_map", "saliency_overlay_u8", "param_stats", "project_poses", "draw_poses_u8", "dropout_begin", "dropout_rows")
 
 
 def _ops():
@@ -324,6 +326,40 @@ def measurement_noise(x0: torch.Tensor, desc: List[float], state: torch.Tensor) 
 @measurement_noise.register_fake
 def _(x0, desc, state):
     return torch.empty_like(x0)
+
+
+# ---- head dropout --------------------------------------------------------------------------------------------------------------
+@torch.library.custom_op(_NS + "::dropout_begin", mutates_args=("state", "picks"), device_types="cuda")
+def dropout_begin(state: torch.Tensor, picks: torch.Tensor) -> None:
+    """picks[0] <- the step counter state[0], which advances by one (int32 device tensors): once per train step"""
+    _ops().dropout_begin(state, picks)
+
+
+@dropout_begin.register_fake
+def _(state, picks):
+    return None
+
+
+@torch.library.custom_op(_NS + "::dropout_rows", mutates_args=(), device_types="cuda")
+def dropout_rows(x: torch.Tensor, desc: List[float], picks: torch.Tensor, site: int, c0: int, c1: int) -> torch.Tensor:
+    """x fp32 (n, cols) -> a copy whose columns [c0, c1) went through inverted dropout with the mask of step picks[0] and of `site`;
+    desc: the seed's low word, its high word, the drop probability p in [0, 1).  The same call masks a gradient."""
+    ops = _ops()
+    if len(desc) != 3:
+        raise ValueError("dropout_rows: desc is seed_lo, seed_hi, p")
+    lo, hi = int(desc[0]), int(desc[1])
+    if not (0 <= lo < 2 ** 32 and 0 <= hi < 2 ** 32):
+        raise ValueError("dropout_rows: the seed travels as two 32-bit words; got %r, %r" % (desc[0], desc[1]))
+    d = ops.dropout_desc(desc[2], lo | (hi << 32))
+    out = x.contiguous().clone()
+    if d.thresh == 0:   # p = 0: nothing is dropped, nothing is launched
+        return out
+    return ops.dropout_rows(out, d, picks, site=site, c0=c0, c1=c1)
+
+
+@dropout_rows.register_fake
+def _(x, desc, picks, site, c0, c1):
+    return torch.empty_like(x, memory_format=torch.contiguous_format)
 
 
 # ---- occlusion sensitivity -----------------------------------------------------------------------------------------------------
