@@ -128,6 +128,12 @@ class LSTMOp:
             lib.rpe_lstm_cell_fwd(ops._p(gates[t]), ops._p(self.b_ih.data), ops._p(self.b_hh.data), ops._p(c_prev), ops._p(cs[t]), ops._p(hs[t]),
                                   N, H, s)
         if save:
+            # a saving forward owns its initial state: the caller's (h0, c0) are the carried tensors of rollout mode, overwritten in
+            # place with (h_T, c_T) before the backward reads them (N x H floats each; training passes None)
+            if h0 is not None:
+                h0 = h0.clone()
+            if c0 is not None:
+                c0 = c0.clone()
             self.S, self.N, self.gates, self.hs, self.cs, self.h0, self.c0 = S, N, gates, hs, cs, h0, c0
         return hs.view(S * N, H), (hs[S - 1], cs[S - 1])
 
