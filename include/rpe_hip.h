@@ -89,7 +89,14 @@ int rpe_conv2d_dgrad(const rpe_conv_desc* d, int dtype, const void* dy, const vo
  * dz[B][H][W][in_c] = (conv_transpose(dy, w) + addend) * [ReLU mask of that layer's output], and per-128-row-tile partial
  * sums (sum dz, sum dz*xhat) -> bn->stats_part [tiles][2][in_c], consumed by rpe_bn_backward_from_dz.
  * mask: a_mask != NULL: its bits;  else a_out != NULL: a_out > 0;  else scale/shift != NULL: y*scale+shift > 0 (BN+ReLU
- * without residual);  else none. */
+ * without residual);  else none.
+ * Rows of stats_part (rpe_conv2d_dgrad_stats_tiles of them, every one written in every column, nothing behind them), by form:
+ *   plain tiles (1x1 / stride 1 and every shape not named below): row t = the rows [128 t, 128 t + 128) of dz [B H W][in_c];
+ *   class-major (stride 2, even in_h and in_w): row cls * ceil(rows_q / 128) + t, cls = 2 (h & 1) + (w & 1), rows_q = B (H/2) (W/2):
+ *     the t-th 128 pixels of that parity class's own list (b, h', w');
+ *   halo tiles (3x3 / stride 1 / pad 1, 16-bit types, out_c % 64 == 0): row t = the rt whole image rows [rt t, rt t + rt) of the
+ *     B * in_h rows, rt * in_w <= 128 pixels.
+ * Consumers may rely on the column totals over all rows only; which pixels a row covers is a contract for the 1x1 / stride-1 form alone. */
 typedef struct {
     const void* y;       /* raw conv output the BN normalised, same shape as dz.  NULL together with a_mask (1x1 / stride-1 convs of a 16-bit
                           * type): that output does not exist -- only sum dz is emitted (the second half of every partial row is 0),

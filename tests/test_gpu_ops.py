@@ -301,7 +301,7 @@ def test_conv_wgrad_many_splits_is_deterministic():
 @pytest.mark.parametrize("dtype", DTYPES)
 @pytest.mark.parametrize("mask_mode", [1, 2, 4])
 @pytest.mark.parametrize("cfg", [(2, 14, 64, 64, 3, 1, 1), (2, 14, 256, 512, 1, 2, 0), (3, 8, 128, 256, 1, 1, 0), (8, 24, 128, 128, 3, 1, 1),
-                                 (6, 30, 64, 1024, 1, 1, 0)])
+                                 (6, 30, 64, 1024, 1, 1, 0), (2, 16, 64, 128, 3, 2, 1)])
 def test_dgrad_with_fused_bn_backward(dtype, mask_mode, cfg):
     """conv data-gradient + ReLU mask + BN-backward reduction in one epilogue == torch's unfused composition."""
     b, h, ci, co, k, s, p = cfg
