@@ -464,6 +464,104 @@ class ResidentEpisodeDataset(RecordedEpisodeDataset):
         return WindowSampler(self, batch_size, sequence_length, stride, shuffle, seed)
 
 
+WORKSPACE_LO = (-0.35, -0.35, 0.8)    # the workspace of `random_poses`
+WORKSPACE_HI = (0.35, 0.35, 1.3)
+
+# six colours per body, all eighteen distinct: which body a pixel shows, and which way the body is turned, can be read off the frame
+BOX_FACE_COLOURS = (((220, 40, 40), (255, 140, 0), (160, 30, 90), (250, 200, 60), (120, 20, 20), (255, 100, 150)),      # own end effector: reds
+                    ((40, 60, 220), (0, 160, 255), (90, 40, 170), (60, 220, 230), (20, 30, 120), (150, 130, 255)),      # other arm: blues
+                    ((40, 180, 60), (160, 230, 40), (20, 110, 70), (200, 255, 150), (10, 70, 20), (100, 200, 160)))     # object: greens
+
+
+def look_at_camera(eye, target, up, vfov_deg, hs, ws):
+    """(3, 4) float64 camera matrix in the overlay's convention ([u w, v w, w] = P [x, y, z, 1], u the column and v the row as stored,
+    row 0 at the top of the picture, pixel centres at integers) of a pinhole camera at `eye` looking at `target`, square pixels,
+    vertical field of view `vfov_deg`, principal point ((ws - 1) / 2, (hs - 1) / 2); w is the distance along the viewing direction"""
+    eye, target, up = (np.asarray(v, dtype=np.float64) for v in (eye, target, up))
+    fwd = (target - eye) / np.linalg.norm(target - eye)
+    right = np.cross(fwd, up)
+    right = right / np.linalg.norm(right)
+    down = np.cross(fwd, right)
+    R = np.stack([right, down, fwd])
+    focal = (hs / 2.0) / math.tan(math.radians(vfov_deg) / 2.0)
+    K = np.array([[focal, 0.0, (ws - 1) / 2.0], [0.0, focal, (hs - 1) / 2.0], [0.0, 0.0, 1.0]])
+    return K @ np.concatenate([R, (-R @ eye)[:, None]], axis=1)
+
+
+class BoxScene:
+    """The scene of rendered episodes (DESIGN.md "Rendered episodes": the specification and its numpy restatement exist, the device
+    renderer does not yet): a camera matrix `P` (3, 4) float64, the frame size, the depth range [near, far], `bodies` -- (half extents,
+    six face colours) each, body g drawn at pose g of a frame -- a checkered ground `plane` (z0, checker size, colour, colour) or None,
+    the `sky` colour and `ss` (1: one ray per pixel, 2: four)."""
+
+    def __init__(self, P, hs, ws, near, far, bodies, plane=None, sky=(150, 180, 220), ss=1):
+        self.P = np.array(P, dtype=np.float64)
+        self.hs, self.ws, self.near, self.far = int(hs), int(ws), float(near), float(far)
+        self.bodies = [(tuple(float(v) for v in h), tuple(tuple(int(v) for v in c) for c in cols)) for h, cols in bodies]
+        self.plane, self.sky, self.ss = plane, tuple(sky), int(ss)
+        if self.P.shape != (3, 4):
+            raise ValueError("BoxScene: P is a (3, 4) camera matrix; got shape {}".format(self.P.shape))
+        if not (1 <= self.hs <= 4096 and 1 <= self.ws <= 4096):
+            raise ValueError("BoxScene: frames are 1..4096 pixels a side; got {} x {}".format(hs, ws))
+        for h, cols in self.bodies:
+            if len(set(cols)) != 6:
+                raise ValueError("BoxScene: a body has six DISTINCT face colours (its orientation is read off them); got {}".format(cols))
+
+    @classmethod
+    def default(cls, hs=256, ws=256, ss=1):
+        """the scene of the rendered task: a camera at (1.6, 0, 1.45) looking at the middle of the workspace of `random_poses` from
+        the front, 45 degrees of vertical field of view; boxes of 10 x 8 x 12 cm for the two end effectors and a 12 cm cube for the
+        object; a grey checkered table 10 cm below the workspace"""
+        P = look_at_camera((1.6, 0.0, 1.45), (0.0, 0.0, 1.0), (0.0, 0.0, 1.0), 45.0, hs, ws)
+        bodies = [((0.05, 0.04, 0.06), BOX_FACE_COLOURS[0]), ((0.05, 0.04, 0.06), BOX_FACE_COLOURS[1]), ((0.06, 0.06, 0.06), BOX_FACE_COLOURS[2])]
+        return cls(P, hs, ws, 0.1, 10.0, bodies, plane=(0.7, 0.1, (110, 110, 110), (170, 170, 170)), sky=(150, 180, 220), ss=ss)
+
+    def camera_matrix(self):
+        """(3, 4) float64: what ops.project_poses / render_episodes take as the camera of frames of this scene"""
+        return self.P.copy()
+
+
+def scene_trajectories(num_episodes, horizon, motion="random", seed=0):
+    """(E, T, 3, 7) float32 poses (x, y, z, qx, qy, qz, qw) of three bodies -- own end effector, other arm, object -- over E episodes of
+    T timesteps, host numpy, from np.random.default_rng(seed) alone.  Starts are uniform in the workspace of `random_poses`;
+    "random": a walk whose velocity is AR(1) (v <- 0.8 v + 0.02 N(0, I)), reflected at the workspace walls; "up": x and y stay, z rises
+    linearly to the top of the workspace; "up_random": the walk in x and y, the rise in z.  The orientation is a random walk on the
+    unit quaternions (q <- normalise(q + 0.1 N(0, I))), stored with w >= 0 (`standardize_quat`)."""
+    if motion not in MOTIONS:
+        raise ValueError("Invalid motion specified. {} supported, {} requested.".format(MOTIONS, motion))
+    e, t = int(num_episodes), int(horizon)
+    if e < 1 or t < 1:
+        raise ValueError("scene_trajectories: at least one episode of one timestep; got {} x {}".format(num_episodes, horizon))
+    rng = np.random.default_rng(int(seed))
+    lo, hi = np.array(WORKSPACE_LO), np.array(WORKSPACE_HI)
+    pos = rng.uniform(lo, hi, size=(e, 3, 3))
+    vel = 0.02 * rng.standard_normal((e, 3, 3))
+    q = rng.standard_normal((e, 3, 4))
+    q /= np.linalg.norm(q, axis=-1, keepdims=True)
+    z_start = pos[..., 2].copy()
+    out = np.empty((e, t, 3, 7), dtype=np.float64)
+    walk = (True, True, motion == "random") if motion != "up" else (False, False, False)
+    for k in range(t):
+        if motion != "random":
+            pos[..., 2] = z_start + (hi[2] - z_start) * (k / (t - 1) if t > 1 else 0.0)
+        out[:, k, :, :3] = pos
+        out[:, k, :, 3:] = np.where(q[..., 3:] < 0, -q, q)
+        step_v = 0.8 * vel + 0.02 * rng.standard_normal((e, 3, 3))
+        step_q = 0.1 * rng.standard_normal((e, 3, 4))
+        vel = step_v
+        for i in range(3):
+            if not walk[i]:
+                continue
+            p = pos[..., i] + vel[..., i]
+            over, under = p > hi[i], p < lo[i]
+            p = np.where(over, 2 * hi[i] - p, np.where(under, 2 * lo[i] - p, p))
+            vel[..., i] = np.where(over | under, -vel[..., i], vel[..., i])
+            pos[..., i] = np.clip(p, lo[i], hi[i])
+        q = q + step_q
+        q /= np.linalg.norm(q, axis=-1, keepdims=True)
+    return out.astype(np.float32)
+
+
 class _DeviceStepCounter:
     """What WindowSampler, FrameAugment, DepthAugment and MeasurementNoise share: `seed`; a step counter that lives in device memory
     once there is a device to keep it on (`_state`, an int32 tensor whose element 0 the launch itself advances) and on the host before
