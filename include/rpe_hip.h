@@ -297,6 +297,38 @@ typedef struct {
 int rpe_augment_frames_u8(const unsigned char* in, unsigned char* out, int B, int Hs, int Ws, const rpe_augment_desc* d, unsigned* state, int* params,
                           unsigned long long* sums, void* stream);
 
+/* Blur of raw camera frames (no counterpart in the reference): defocus (Gaussian) and linear motion blur on uint8 [B][Hs][Ws][3]
+ * frames, uint8 out, run IN FRONT of rpe_augment_frames_u8 -- optics first, then photometry, noise and the occluder.  All arithmetic
+ * is integer and specified to the bit ("Frame blur"); coordinates are clamped to the frame (replicate border).
+ *   Gaussian, level s: radius R = radius[s] <= 8, half-kernel w = taps[s][0..R] >= 0 with w[0] + 2 (w[1] + .. + w[R]) = 2048;
+ *     h(x, y) = sum_{k=-R..R} w[|k|] v(x + k, y);  out(x, y) = (sum_{k=-R..R} w[|k|] h(x, y + k) + 2^21) >> 22
+ *   motion, odd length L = 3 .. 15, direction d: for t = -(L-1)/2 .. (L-1)/2, dx = (t dir_cx[d] + 128) >> 8, dy = (t dir_cy[d] + 128) >> 8
+ *     (floor shifts);  out = (2 sum_t v(x + dx, y + dy) + L) / (2 L)
+ * Each stream g (frame b, or b % group) draws r0..r3 = Philox4x32-10(key = seed, counter (g, 0, step, 0x424C5552 "BLUR")):
+ *   kind = r0 < gauss_thresh ? 1 : ((u64)r0 < (u64)gauss_thresh + motion_thresh ? 2 : 0)   (0: the frame is copied)
+ *   level = (r1 n_levels) >> 32,  L = 3 + 2 ((r2 n_lengths) >> 32),  d = (r3 n_dirs) >> 32 */
+typedef struct {
+    unsigned long long seed;
+    unsigned gauss_thresh, motion_thresh;         /* a stream is blurred iff its word r0 is below ...; the sum is at most 2^32 - 1 */
+    int n_levels;                                 /* 1 .. 8 */
+    int radius[8];                                /* 0 .. 8 per level */
+    int taps[8][9];                               /* taps[s][k], k <= radius[s]; entries beyond the radius are ignored */
+    int n_lengths;                                /* 1 .. 7: L in {3, 5, .., 1 + 2 n_lengths} */
+    int n_dirs;                                   /* 1 .. 16 */
+    int dir_cx[16], dir_cy[16];                   /* Q8 direction components, each within +-256 */
+    int group;                                    /* 0: frame b draws from stream b; N > 0: from stream b % N */
+} rpe_blur_desc;
+/* in / out: device, [B][Hs][Ws][3], DISJOINT (a stencil cannot run in place); Hs * Ws < 2^32.  state: device, state[0] is the step
+ * counter -- the launch READS it and never advances it: the rpe_augment_frames_u8 call that follows does, so both tables of one
+ * step carry the same [0] and a captured pair draws fresh numbers at every replay.  params: device, 1 + 4 G ints (G = B, or `group`),
+ * receives [0] = the step used, then per stream kind, level, L, d.  Refused with RPE_ERR_SHAPE before any launch: a null pointer,
+ * non-positive sizes, Hs * Ws >= 2^32, n_levels outside 1..8, a radius outside 0..8, a negative tap or a level whose taps do not sum
+ * to 2048, n_lengths outside 1..7, n_dirs outside 1..16, a direction component beyond +-256, thresholds whose sum exceeds 2^32 - 1,
+ * group < 0, in and out overlapping.  4-byte loads and stores where both pointers and the pixel rows (Ws % 4 == 0) are 4-byte
+ * aligned, bytes otherwise.  Two launches. */
+int rpe_blur_frames_u8(const unsigned char* in, unsigned char* out, int B, int Hs, int Ws, const rpe_blur_desc* d, const unsigned* state, int* params,
+                       void* stream);
+
 /* Shuffled minibatches from recorded episodes resident in device memory (no counterpart in the reference, whose DataLoader walks the
  * episodes in lockstep, unshuffled): an index launch and a row gather in front of rpe_augment_frames_u8 / rpe_stage_frames_u8[_resized].
  * All arithmetic is unsigned / 64-bit integer and specified to the bit ("Minibatch sampling").

@@ -50,6 +50,12 @@ class AugmentDesc(Structure):
                 + [("fill_rgb", ctypes.c_ubyte * 3), ("group", c_int)])
 
 
+class BlurDesc(Structure):
+    """rpe_blur_desc"""
+    _fields_ = [("seed", ctypes.c_ulonglong), ("gauss_thresh", ctypes.c_uint), ("motion_thresh", ctypes.c_uint), ("n_levels", c_int), ("radius", c_int * 8),
+                ("taps", (c_int * 9) * 8), ("n_lengths", c_int), ("n_dirs", c_int), ("dir_cx", c_int * 16), ("dir_cy", c_int * 16), ("group", c_int)]
+
+
 class SampleDesc(Structure):
     """rpe_sample_desc"""
     _fields_ = [("seed", ctypes.c_ulonglong)] + [(n, c_int) for n in ("E", "T", "S", "stride", "N", "shuffle")]
@@ -139,6 +145,7 @@ _SPEC = {
     "rpe_stage_frames_u8_resized": (I, [I, P, P, I, I, I, I, I, I, I, I, I, P, P, I, P, P, I, P, POINTER(c_float), POINTER(c_float), P]),
     "rpe_stage_depth_f32_resized": (I, [P, P, I, I, I, I, I, I, I, I, I, P, P, I, P, P, I, P]),
     "rpe_augment_frames_u8": (I, [P, P, I, I, I, POINTER(AugmentDesc), P, P, P, P]),
+    "rpe_blur_frames_u8": (I, [P, P, I, I, I, POINTER(BlurDesc), P, P, P]),
     "rpe_augment_depth_f32": (I, [P, P, I, I, I, POINTER(DepthAugmentDesc), P, P, P, I, P]),
     "rpe_sample_windows": (I, [POINTER(SampleDesc), P, P, P, P]),
     "rpe_sample_windows_ragged": (I, [POINTER(SampleDesc), P, P, P, P, P]),

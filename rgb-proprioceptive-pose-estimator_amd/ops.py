@@ -972,6 +972,90 @@ def augment_frames_u8(frames, desc, state, out=None, params=None, sums=None):
     return out
 
 
+BLUR_MAX_LEVELS, BLUR_MAX_RADIUS, BLUR_MAX_DIRS, BLUR_TAP_SUM = 8, 8, 16, 2048
+BLUR_DESC_FIELDS = ("seed", "gauss_thresh", "motion_thresh", "radius", "taps", "n_lengths", "dir_cx", "dir_cy", "group")
+BLUR_DESC_NUMBERS = 4 + BLUR_MAX_LEVELS * (2 + BLUR_MAX_RADIUS) + 2 + 2 * BLUR_MAX_DIRS + 1   # the flat list of torch.ops.rpe.blur_frames_u8
+
+
+def blur_desc(seed=0, gauss_thresh=0, motion_thresh=0, radius=(0,), taps=((BLUR_TAP_SUM,),), n_lengths=1, dir_cx=(256,), dir_cy=(0,), group=0):
+    """rpe_blur_desc from plain integers (the defaults blur nothing): radius[s] and taps[s][0 .. radius[s]] per Gaussian level
+    (n_levels = len(radius)), the Q8 components dir_cx[d], dir_cy[d] per motion direction (n_dirs = len(dir_cx)), n_lengths motion
+    lengths 3, 5, ...  Counts and tables that do not fit the struct are refused here; their values by the entry point."""
+    from ._lib import BlurDesc
+    d = BlurDesc()
+    d.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    for k, v in (("gauss_thresh", gauss_thresh), ("motion_thresh", motion_thresh)):
+        if not 0 <= int(v) < 2 ** 32:
+            raise ValueError("blur_desc: %s is an unsigned 32-bit word; got %r" % (k, v))
+        setattr(d, k, int(v))
+    radius, taps, dir_cx, dir_cy = list(radius), [list(t) for t in taps], list(dir_cx), list(dir_cy)
+    if not 1 <= len(radius) <= BLUR_MAX_LEVELS or len(taps) != len(radius):
+        raise ValueError("blur_desc: 1 to %d levels, one row of taps each; got %d radii and %d rows" % (BLUR_MAX_LEVELS, len(radius), len(taps)))
+    if not 1 <= len(dir_cx) <= BLUR_MAX_DIRS or len(dir_cy) != len(dir_cx):
+        raise ValueError("blur_desc: 1 to %d directions with both components; got %d and %d" % (BLUR_MAX_DIRS, len(dir_cx), len(dir_cy)))
+    d.n_levels, d.n_lengths, d.n_dirs, d.group = len(radius), int(n_lengths), len(dir_cx), int(group)
+    for s, (r, row) in enumerate(zip(radius, taps)):
+        if len(row) > BLUR_MAX_RADIUS + 1:
+            raise ValueError("blur_desc: a level has at most %d taps; got %d" % (BLUR_MAX_RADIUS + 1, len(row)))
+        d.radius[s] = int(r)
+        for k, w in enumerate(row):
+            d.taps[s][k] = int(w)
+    for i, (cx, cy) in enumerate(zip(dir_cx, dir_cy)):
+        d.dir_cx[i], d.dir_cy[i] = int(cx), int(cy)
+    return d
+
+
+def blur_desc_numbers(seed=0, gauss_thresh=0, motion_thresh=0, radius=(0,), taps=((BLUR_TAP_SUM,),), n_lengths=1, dir_cx=(256,), dir_cy=(0,), group=0):
+    """blur_desc's arguments as the flat list of BLUR_DESC_NUMBERS integers `torch.ops.rpe.blur_frames_u8` takes: seed (as a signed
+    64-bit value), gauss_thresh, motion_thresh, n_levels, 8 radii, 8 x 9 taps, n_lengths, n_dirs, 16 + 16 components, group"""
+    d = blur_desc(seed, gauss_thresh, motion_thresh, radius, taps, n_lengths, dir_cx, dir_cy, group)   # (checks the counts)
+    seed = d.seed - (1 << 64) if d.seed >= (1 << 63) else d.seed
+    return ([seed, d.gauss_thresh, d.motion_thresh, d.n_levels] + list(d.radius) + [w for row in d.taps for w in row] + [d.n_lengths, d.n_dirs]
+            + list(d.dir_cx) + list(d.dir_cy) + [d.group])
+
+
+def blur_desc_from_numbers(numbers):
+    """the inverse of blur_desc_numbers -> rpe_blur_desc"""
+    n = [int(v) for v in numbers]
+    if len(n) != BLUR_DESC_NUMBERS:
+        raise ValueError("blur_frames_u8: desc has %d integers (ops.blur_desc_numbers); got %d" % (BLUR_DESC_NUMBERS, len(n)))
+    levels, dirs = n[3], n[85]
+    if not 1 <= levels <= BLUR_MAX_LEVELS or not 1 <= dirs <= BLUR_MAX_DIRS:
+        raise ValueError("blur_frames_u8: desc names %d levels and %d directions" % (levels, dirs))
+    return blur_desc(seed=n[0], gauss_thresh=n[1], motion_thresh=n[2], radius=n[4:4 + levels], taps=[n[12 + 9 * s:21 + 9 * s] for s in range(levels)],
+                     n_lengths=n[84], dir_cx=n[86:86 + dirs], dir_cy=n[102:102 + dirs], group=n[118])
+
+
+def blur_frames_u8(frames, desc, state, out=None, params=None):
+    """frames uint8 (..., Hs, Ws, 3) contiguous -> the blurred frames, uint8 of the same shape (rpe_blur_frames_u8: per stream no
+    blur, a Gaussian level or a linear motion blur, in integer arithmetic with a replicate border).  desc: blur_desc(...).  state:
+    int32 device tensor whose element 0 is the step counter; the launch reads it and does NOT advance it (augment_frames_u8, which
+    follows, does).  out: destination, disjoint from `frames`.  params: int32 (1 + 4 G,) device tensor receiving [0] the step used,
+    then per stream kind, level, L, d (allocated when not given)."""
+    if frames.dtype != torch.uint8 or frames.dim() < 4 or frames.shape[-1] != 3:
+        raise ValueError("blur_frames_u8: frames must be uint8 (..., Hs, Ws, 3); got %s %r" % (frames.dtype, tuple(frames.shape)))
+    _chk(frames, "frames")
+    hs, ws = frames.shape[-3:-1]
+    b = frames.numel() // (hs * ws * 3) if hs * ws else 0
+    if b == 0:
+        raise ValueError("blur_frames_u8: empty batch")
+    g = augment_streams(desc, b)
+    dev = frames.device
+    if state.dtype != torch.int32 or state.numel() < 1 or state.device != dev:
+        raise ValueError("blur_frames_u8: state must be an int32 tensor on the frames' device")
+    if out is None:
+        out = torch.empty_like(frames)
+    elif out.dtype != torch.uint8 or out.shape != frames.shape or out.device != dev:
+        raise ValueError("blur_frames_u8: out must be uint8 of the frames' shape on their device")
+    _chk(out, "out")
+    if params is None:
+        params = torch.empty(1 + 4 * g, dtype=torch.int32, device=dev)
+    elif params.dtype != torch.int32 or params.numel() < 1 + 4 * g or params.device != dev:
+        raise ValueError("blur_frames_u8: params must be int32 with at least %d elements" % (1 + 4 * g))
+    lib.rpe_blur_frames_u8(_p(frames), _p(out), b, hs, ws, ctypes.byref(desc), _p(_chk(state, "state")), _p(_chk(params, "params")), _stream())
+    return out
+
+
 DEPTH_AUGMENT_DESC_FIELDS = ("seed", "n0", "n1", "n2", "q", "inv_q", "lo", "hi", "drop_thresh", "hole_lo", "hole_hi", "hh_lo", "hh_hi", "hw_lo", "hw_hi",
                              "hole_value", "occluder_value", "group")
 DEPTH_AUGMENT_DESC_NUMBERS = ("seed_lo", "seed_hi") + DEPTH_AUGMENT_DESC_FIELDS[1:]   # the flat list of torch.ops.rpe.augment_depth_f32

@@ -9,7 +9,8 @@ Added flags: --dtype {bf16,f16,f32}, --optimizer {fused,torch}, --max_grad_norm,
 learning-rate schedule (--lr_schedule, --warmup_steps, --warmup_start_factor, --lr_total_steps, --lr_min_factor, --lr_step_size,
 --lr_gamma), --trunk_lr_scale (the trunk as a param group of its own) and --ema_decay (writes `<checkpoint>.ema` beside the raw weights);
 the on-device frame augmentation of recorded episodes (--aug_brightness, --aug_contrast, --aug_saturation, --aug_noise_std,
---aug_erase_prob, --aug_erase_scale, --aug_erase_fill, --aug_per_frame, --aug_seed; all off by default, they need --episodes) and of
+--aug_erase_prob, --aug_erase_scale, --aug_erase_fill, --aug_blur_prob, --aug_blur_sigma, --aug_motion_prob, --aug_motion_max_length,
+--aug_per_frame, --aug_seed; all off by default, they need --episodes) and of
 their depth frames (--aug_depth_noise, --aug_depth_drop_prob, --aug_depth_holes, --aug_depth_hole_scale, --aug_depth_hole_value,
 --aug_depth_quant, --aug_depth_clamp, --aug_depth_share_erase, --aug_depth_occluder_value; off by default, they need --use_depth --episodes);
 --resident (the --episodes file lives in HBM; an --episodes file of episodes of unequal length needs it and --batch_size) and, with it, --batch_size, --window_stride, --shuffle_seed (shuffled minibatches drawn on the
@@ -98,6 +99,11 @@ def build_parser():
     p.add_argument("--aug_erase_scale", type=float, nargs=2, default=None, metavar=("LO", "HI"),
                    help="augmentation: each side of the erased rectangle as a fraction of the frame's (default 0.1 0.3)")
     p.add_argument("--aug_erase_fill", type=str, default=None, help="augmentation: 'mean' (ImageNet mean, the default), 'noise' (random bytes) or R,G,B bytes")
+    p.add_argument("--aug_blur_prob", type=float, default=None, metavar="P", help="augmentation: probability of a Gaussian (defocus) blur per frame (default: off)")
+    p.add_argument("--aug_blur_sigma", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                   help="augmentation: the Gaussian blur's sigma range in pixels, 0 <= LO <= HI <= 4 (default 0.5 2.0)")
+    p.add_argument("--aug_motion_prob", type=float, default=None, metavar="P", help="augmentation: probability of a linear motion blur per frame (default: off)")
+    p.add_argument("--aug_motion_max_length", type=int, default=None, metavar="L", help="augmentation: the longest motion blur in pixels, odd, 3 .. 15 (default 9)")
     p.add_argument("--aug_per_frame", action="store_true",
                    help="augmentation: draw jitter and occluder per frame (default: per episode, kept through a chunk of --sequence_length steps)")
     p.add_argument("--aug_seed", type=int, default=None, help="augmentation: seed of the device generator (default 0; rank r uses seed + r)")
@@ -205,13 +211,14 @@ def build_sampling(args):
 
 
 AUGMENT_FLAGS = ("aug_brightness", "aug_contrast", "aug_saturation", "aug_noise_std", "aug_erase_prob", "aug_erase_scale", "aug_erase_fill", "aug_seed")
+BLUR_FLAGS = ("aug_blur_prob", "aug_blur_sigma", "aug_motion_prob", "aug_motion_max_length")
 
 
 def build_augment(args, rank=0):
     """the --aug_* family -> util.data_utils.FrameAugment, or None when none of its flags is given.  The flags need --episodes: the
     synthetic episodes are preprocessed float images, which the augmentation does not take."""
     from rgb_proprioceptive_pose_estimator_amd.util.data_utils import FrameAugment
-    given = {k: getattr(args, k, None) for k in AUGMENT_FLAGS}
+    given = {k: getattr(args, k, None) for k in AUGMENT_FLAGS + BLUR_FLAGS}
     if all(v is None for v in given.values()) and not getattr(args, "aug_per_frame", False):
         return None
     if not getattr(args, "episodes", None):
@@ -226,7 +233,9 @@ def build_augment(args, rank=0):
         return FrameAugment(brightness=given["aug_brightness"] or 0.0, contrast=given["aug_contrast"] or 0.0, saturation=given["aug_saturation"] or 0.0,
                             noise_std=given["aug_noise_std"] or 0.0, erase_prob=given["aug_erase_prob"] or 0.0,
                             erase_scale=tuple(given["aug_erase_scale"] or (0.1, 0.3)), erase_fill=fill, per_episode=not args.aug_per_frame,
-                            seed=(given["aug_seed"] or 0) + rank)
+                            seed=(given["aug_seed"] or 0) + rank, blur_prob=given["aug_blur_prob"] or 0.0,
+                            blur_sigma=tuple(given["aug_blur_sigma"] or (0.5, 2.0)), motion_blur_prob=given["aug_motion_prob"] or 0.0,
+                            motion_blur_max_length=9 if given["aug_motion_max_length"] is None else given["aug_motion_max_length"])
     except ValueError as e:
         raise SystemExit("--aug_*: %s" % e)
 

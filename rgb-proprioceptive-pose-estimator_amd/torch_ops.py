@@ -18,6 +18,7 @@ ResNet; models/losses.py:114-128 is the loss; util/learn_utils.py:152-184 the st
     rpe::adam_step                                  torch.optim.Adam's update of one flat fp32 tensor, in place
     rpe::param_stats                                torch._foreach_norm over gradients and parameters, isfinite / zero counts and the update norm per tensor, two launches
     rpe::augment_frames_u8                          (no counterpart: the reference does not augment) jitter, noise and erasing of raw uint8 frames
+    rpe::blur_frames_u8                             (no counterpart) defocus and motion blur of raw uint8 frames, in front of rpe::augment_frames_u8
     rpe::augment_depth_f32                          (no counterpart) depth-sensor model on raw fp32 depth: range noise, quantisation, clamp, dropout, holes, the RGB occluder
     rpe::sample_windows / gather_rows               DataLoader(shuffle=True) over episode windows resident in HBM: the batch's index, and its rows
     rpe::sample_windows_ragged / pose_loss_masked / (no counterpart: the reference's episodes all have one length) the window index, the summed loss and the
@@ -40,7 +41,7 @@ import torch
 __all__ = ["NAMES"]
 
 _NS = "rpe"
-NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step", "augment_frames_u8", "augment_depth_f32", "sample_windows", "gather_rows",
+NAMES = ("conv2d_fwd", "conv2d_dgrad", "conv2d_wgrad", "conv2d", "bn_apply", "linear_fwd", "pose_loss", "pose_distance_loss", "pose_errors", "adam_step", "augment_frames_u8", "blur_frames_u8", "augment_depth_f32", "sample_windows", "gather_rows",
          "sample_windows_ragged", "pose_loss_masked", "error_stats_ragged", "measurement_noise", "occlude_grid_u8", "pose_displacement", "saliency_map", "saliency_overlay_u8", "param_stats", "project_poses", "draw_poses_u8", "dropout_begin", "dropout_rows")
 
 
@@ -216,6 +217,19 @@ def augment_frames_u8(frames: torch.Tensor, desc: List[int], state: torch.Tensor
 
 
 @augment_frames_u8.register_fake
+def _(frames, desc, state):
+    return torch.empty_like(frames)
+
+
+@torch.library.custom_op(_NS + "::blur_frames_u8", mutates_args=(), device_types="cuda")
+def blur_frames_u8(frames: torch.Tensor, desc: List[int], state: torch.Tensor) -> torch.Tensor:
+    """frames uint8 (..., Hs, Ws, 3) -> blurred uint8 frames; desc: the integers of rpe_blur_desc as ops.blur_desc_numbers(...) lists
+    them; state: int32, element 0 is the step counter, read and NOT advanced (rpe::augment_frames_u8, which follows, advances it)"""
+    ops = _ops()
+    return ops.blur_frames_u8(frames, ops.blur_desc_from_numbers(desc), state)
+
+
+@blur_frames_u8.register_fake
 def _(frames, desc, state):
     return torch.empty_like(frames)
 

@@ -718,6 +718,31 @@ def _jitter_range(name, amount):
     return _q16(max(0.0, 1.0 - a)), _q16(1.0 + a)
 
 
+BLUR_LEVELS, BLUR_DIRS, BLUR_MAX_RADIUS, BLUR_TAP_SUM = 8, 16, 8, 2048
+
+
+def blur_gaussian_taps(sigma):
+    """(R, [w_0 .. w_R]): the integer half-kernel of a Gaussian of standard deviation `sigma` pixels as rpe_blur_frames_u8 takes it --
+    R = min(8, max(1, ceil(3 sigma))), w_k = round(2048 g_k / sum g) with g_k = exp(-k^2 / 2 sigma^2) over k = -R .. R, and w_0 set
+    so that w_0 + 2 (w_1 + .. + w_R) = 2048 exactly.  sigma = 0: R = 0, the identity."""
+    sigma = float(sigma)
+    if not 0.0 <= sigma <= 4.0:
+        raise ValueError("a blur sigma must lie in [0, 4] pixels; got {!r}".format(sigma))
+    if sigma == 0.0:
+        return 0, [BLUR_TAP_SUM]
+    r = min(BLUR_MAX_RADIUS, max(1, int(math.ceil(3.0 * sigma))))
+    g = [math.exp(-k * k / (2.0 * sigma * sigma)) for k in range(r + 1)]
+    total = g[0] + 2.0 * sum(g[1:])
+    w = [int(round(BLUR_TAP_SUM * v / total)) for v in g]
+    w[0] = BLUR_TAP_SUM - 2 * sum(w[1:])
+    return r, w
+
+
+def blur_directions(nd=BLUR_DIRS):
+    """the Q8 components (cx, cy) of `nd` motion directions over 180 degrees: round(256 cos(pi d / nd)), round(256 sin(pi d / nd))"""
+    return ([int(round(256.0 * math.cos(math.pi * d / nd))) for d in range(nd)], [int(round(256.0 * math.sin(math.pi * d / nd))) for d in range(nd)])
+
+
 class FrameAugment(_DeviceStepCounter):
     """Label-preserving augmentation of raw uint8 camera frames on the device (rpe_augment_frames_u8; DESIGN.md "Frame
     augmentation"): brightness / contrast / saturation jitter with torchvision's ranges (`brightness=b`: a factor in
@@ -726,15 +751,19 @@ class FrameAugment(_DeviceStepCounter):
     which normalises to ~0), "noise" (random bytes) or an (r, g, b) tuple.  No crop, shift or flip: the labels are absolute poses
     seen by a fixed camera.  The random numbers are drawn on the device from (seed, step); the step counter lives in device memory
     and every call advances it, also a call replayed from a captured graph.
-    per_episode: frames (S, N, Hs, Ws, 3) share their jitter and occluder along S (one episode keeps them through the chunk); the
-    noise is always per frame.  A 4-D batch (B, Hs, Ws, 3) draws per frame.
+    Blur (rpe_blur_frames_u8; DESIGN.md "Frame blur") runs in front of all that, optics first: with probability `blur_prob` a frame
+    is defocused by a Gaussian whose sigma is one of 8 levels spread over `blur_sigma` = (lo, hi) pixels, with probability
+    `motion_blur_prob` it is smeared along one of 16 directions over an odd length of 3 .. `motion_blur_max_length` pixels, otherwise
+    it stays sharp.  With both probabilities 0 (the default) no blur launch is issued.
+    per_episode: frames (S, N, Hs, Ws, 3) share their jitter, blur and occluder along S (one episode keeps them through the chunk);
+    the noise is always per frame.  A 4-D batch (B, Hs, Ws, 3) draws per frame.
 
         aug = FrameAugment(brightness=0.2, contrast=0.2, noise_std=2.0, erase_prob=0.25)
         frames = aug(frames)                # uint8 device frames -> a new uint8 tensor of the same shape
     """
 
     def __init__(self, brightness=0., contrast=0., saturation=0., noise_std=0., erase_prob=0., erase_scale=(0.1, 0.3), erase_fill="mean",
-                 per_episode=True, seed=0):
+                 per_episode=True, seed=0, blur_prob=0., blur_sigma=(0.5, 2.0), motion_blur_prob=0., motion_blur_max_length=9):
         self.qb = _jitter_range("brightness", brightness)
         self.qc = _jitter_range("contrast", contrast)
         self.qs = _jitter_range("saturation", saturation)
@@ -763,8 +792,29 @@ class FrameAugment(_DeviceStepCounter):
                 raise ValueError('erase_fill is "mean", "noise" or an (r, g, b) tuple of bytes; got {!r}'.format(erase_fill))
             self.fill_mode, self.fill_rgb = 0, rgb
         self.per_episode = bool(per_episode)
+        pg, pm = float(blur_prob), float(motion_blur_prob)
+        if not (0.0 <= pg <= 1.0 and 0.0 <= pm <= 1.0 and pg + pm <= 1.0):
+            raise ValueError("blur_prob and motion_blur_prob must lie in [0, 1] with a sum of at most 1; got {!r}, {!r}".format(blur_prob, motion_blur_prob))
+        self.gauss_thresh = min(2 ** 32 - 1, int(round(pg * 2 ** 32)))
+        self.motion_thresh = min(2 ** 32 - 1 - self.gauss_thresh, int(round(pm * 2 ** 32)))
+        try:
+            lo, hi = (float(v) for v in blur_sigma)
+        except (TypeError, ValueError):
+            raise ValueError("blur_sigma is (lo, hi) in pixels; got {!r}".format(blur_sigma))
+        if not 0.0 <= lo <= hi <= 4.0:
+            raise ValueError("blur_sigma must be (lo, hi) with 0 <= lo <= hi <= 4; got {!r}".format(blur_sigma))
+        self.blur_sigma = (lo, hi)
+        ns = 1 if lo == hi else BLUR_LEVELS
+        self.blur_sigmas = [lo + (hi - lo) * s / (ns - 1) if ns > 1 else lo for s in range(ns)]
+        self.blur_levels = [blur_gaussian_taps(v) for v in self.blur_sigmas]   # (R, taps) per level
+        if isinstance(motion_blur_max_length, bool) or int(motion_blur_max_length) != motion_blur_max_length or not 3 <= motion_blur_max_length <= 15 \
+                or motion_blur_max_length % 2 == 0:
+            raise ValueError("motion_blur_max_length must be an odd integer in [3, 15]; got {!r}".format(motion_blur_max_length))
+        self.motion_blur_max_length = int(motion_blur_max_length)
+        self.blur_dirs = blur_directions()
         super().__init__(seed)
         self.last_params = None     # device table of the last call: [0] the step used, then per stream qb qc qs erase top left h w
+        self.last_blur_params = None   # device table of the last call's blur: [0] the step used, then per stream kind level L d (None: blur off)
         self.last_geometry = None   # (Hs, Ws, frames, group) of the last call
 
     def erase_bounds(self, size):
@@ -778,6 +828,17 @@ class FrameAugment(_DeviceStepCounter):
         return dict(seed=self.seed, qb_lo=self.qb[0], qb_hi=self.qb[1], qc_lo=self.qc[0], qc_hi=self.qc[1], qs_lo=self.qs[0], qs_hi=self.qs[1],
                     noise_q=self.noise_q, erase_thresh=self.erase_thresh, eh_lo=eh_lo, eh_hi=eh_hi, ew_lo=ew_lo, ew_hi=ew_hi, fill_mode=self.fill_mode,
                     fill_r=self.fill_rgb[0], fill_g=self.fill_rgb[1], fill_b=self.fill_rgb[2], group=int(group))
+
+    @property
+    def blurs(self):
+        """whether a call issues the blur launches"""
+        return self.gauss_thresh != 0 or self.motion_thresh != 0
+
+    def blur_desc_fields(self, group=0):
+        """the arguments of ops.blur_desc (rpe_blur_desc)"""
+        return dict(seed=self.seed, gauss_thresh=self.gauss_thresh, motion_thresh=self.motion_thresh, radius=[r for r, _ in self.blur_levels],
+                    taps=[list(w) for _, w in self.blur_levels], n_lengths=(self.motion_blur_max_length - 1) // 2, dir_cx=list(self.blur_dirs[0]),
+                    dir_cy=list(self.blur_dirs[1]), group=int(group))
 
     @staticmethod
     def check_frames(frames):
@@ -798,6 +859,11 @@ class FrameAugment(_DeviceStepCounter):
         state = self._device_state(frames.device)
         params, sums = self._kept((b, group, frames.device), lambda: (torch.empty(1 + 8 * (group or b), dtype=torch.int32, device=frames.device),
                                                                       torch.empty(b, dtype=torch.int64, device=frames.device)))
+        if self.blurs:   # optics first: the blur reads the step counter, the augmentation launch behind it advances it
+            blurred, bparams = self._kept(("blur", tuple(frames.shape), group, frames.device),
+                                          lambda: (torch.empty_like(frames), torch.empty(1 + 4 * (group or b), dtype=torch.int32, device=frames.device)))
+            frames = ops.blur_frames_u8(frames, ops.blur_desc(**self.blur_desc_fields(group)), state, out=blurred, params=bparams)
+            self.last_blur_params = bparams
         out = ops.augment_frames_u8(frames, ops.augment_desc(**self.desc_fields(hs, ws, group)), state, out=out, params=params, sums=sums)
         self.last_params = params
         self.last_geometry = (int(hs), int(ws), int(b), int(group))   # what DepthAugment(share_erase=self) checks its own batch against
